@@ -7,8 +7,19 @@ paths per pixel: sample 0 is never traced, sampler.go:29-34), Path(maxDepth 10,
 rr 1, Uniform), 16-px tiles, EXACT mode (the reference's per-tile RNG replayed
 bit for bit). Inputs (scene, BVH) are resident on the GPU before timing.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run does what the headline figure needs and no more: scene and context,
+the context's first (schedule-probing) frame, W warmup frames, K timed frames,
+the result line. --full adds the legs that take runs of their own: the frames
+in the other mode (side_mode), the per-request leg (rpc) and the CPU baseline
+(cpu_baseline); --no-side-mode / --no-rpc / --no-cpu-baseline drop one of them.
+
+--dump-outputs DIR writes what the last timed frame left in the caller's film
+(on rank 0: after the reduce) as DIR/film.npy, float64. Scenes are built from
+fixed seeds and EXACT frames are deterministic, so two builds run with the same
+arguments can be compared value for value.
 
 Multi-GPU: one process per GPU; tiles are sharded t -> rank (t mod N) and the
 per-rank fp64 XYZ films are summed on rank 0 with one RCCL reduce (the
@@ -55,17 +66,24 @@ def parse():
     ap.add_argument("--kernel", default="auto", choices=["auto", "serial", "wave", "wavefront", "wave_ci"])
     ap.add_argument("--tiles-per-wave", type=int, default=0, help="k_chain_ci tiles per wave (0 = library default)")
     ap.add_argument("--occupancy", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side mode, the per-request leg (rpc) and the CPU "
+                         "baseline (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the film the last timed step produced as DIR/film.npy (float64; a fixed, seeded "
+                         "pixel sample of a film larger than DUMP_MAX_BYTES)")
     ap.add_argument("--cpu-seconds", type=float, default=30.0, help="wall budget of the CPU baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline (0 = nproc / 8, the host's share per GPU of an 8-GPU node, "
                          "capped by the CPUs this process may use)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--mode", default="exact", choices=["exact", "throughput"],
                     help="mode of the headline line (exact = the reference's per-tile RNG, bit-exact)")
     ap.add_argument("--no-side-mode", action="store_true",
-                    help="skip the extra frames in the other mode (reported under side_mode)")
+                    help="with --full: skip the extra frames in the other mode (reported under side_mode)")
     ap.add_argument("--no-rpc", action="store_true",
-                    help="skip the per-request leg (rpc: fresh scene + context + frame + film download + RGBA8)")
+                    help="with --full: skip the per-request leg (rpc: fresh scene + context + frame + film download "
+                         "+ RGBA8)")
     return ap.parse_args()
 
 
@@ -491,8 +509,31 @@ def timed(step, backend, world, rank, steps, warmup, label="exact", log=sys.stde
     return elapsed, paths_local, paths_total, stats
 
 
+DUMP_MAX_BYTES = 60_000_000   # of --dump-outputs in all (the 1080p film is 49.8 MB)
+
+
+def dump_outputs(out_dir, film):
+    """--dump-outputs: the caller's film after the last timed step, as
+    DIR/film.npy, float64 [H, W, 3] XYZ sums. A film over DUMP_MAX_BYTES
+    (config E: 199 MB) is written as [n, 3]: its pixels at a fixed sample of
+    row-major pixel indices (PCG64 seed 0, without replacement, ascending),
+    the same for every run of the same frame size."""
+    import numpy as np
+
+    a = film.detach().cpu().numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        H, W, C = a.shape
+        n = DUMP_MAX_BYTES // (C * a.itemsize)
+        idx = np.sort(np.random.default_rng(0).choice(H * W, size=n, replace=False))
+        a = a.reshape(H * W, C)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "film.npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be at least 1 and --warmup at least 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -556,8 +597,10 @@ def main():
     kernel_kind = int(stats[0].kernel)
     rays_c = sum(int(s.rays_closest) for s in stats)
     rays_s = sum(int(s.rays_shadow) for s in stats)
+    if args.dump_outputs and rank == 0:   # before any other frame lands in the film
+        dump_outputs(args.dump_outputs, film)
     side = None
-    if not args.no_side_mode:
+    if args.full and not args.no_side_mode:
         other = "throughput" if args.mode == "exact" else "exact"
         e2, _, p2, st2 = timed(make_step(renderer, backend, film, rd_of(other), world), backend, world, rank,
                                2, 1, other)
@@ -567,7 +610,7 @@ def main():
                         "(not bitwise) the reference image; EXACT is the headline"}
 
     rpc = None
-    if world == 1 and not args.no_rpc:
+    if args.full and world == 1 and not args.no_rpc:
         rpc = rpc_leg(G, cfg, W, H, rd_of(args.mode), local, args, elapsed / args.steps * 1e3)
 
     if rank == 0:
@@ -590,7 +633,7 @@ def main():
             "ms_per_step": elapsed / args.steps * 1e3,
             "timed_region": "render_async_into a device-resident film + synchronize per frame (inputs resident "
                             "in HBM); the 50 MB device-to-host film copy of pbrt_gpu_render is excluded here and "
-                            "included in rpc.*.render_ms",
+                            "included in rpc.*.render_ms (--full)",
             "higher_is_better": True,
             "scaling": "strong",
             "vs_baseline": None,
@@ -630,7 +673,7 @@ def main():
             out["side_mode"] = side
         if rpc:
             out["rpc"] = rpc
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             cb = cpu_baseline(args, cfg["scene"], rd_kwargs, W, H, scene)
             cb["gpu_over_cpu"] = value / cb["value"]
             if "per_gpu_share" in cb:

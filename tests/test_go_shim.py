@@ -6,17 +6,18 @@ the Go code uses (functions, types, constants, and the struct fields it sets
 or reads) exists in include/pbrt_gpu.h / include/pbrt_scene.h, so the shim
 cannot drift from the headers.
 """
+import hashlib
+import json
 import os
 import re
+import shutil
 import subprocess
-
-import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SHIM_DIR = os.path.join(REPO, "integration", "go", "pbrtgpu")
 SHIMS = sorted(os.path.join(SHIM_DIR, f) for f in os.listdir(SHIM_DIR) if f.endswith(".go"))
 PATCHES = os.path.join(REPO, "integration", "go", "patches")
-REFERENCE = "/root/reference"
+REFERENCE = os.environ.get("GO_PBRT_REFERENCE", "")   # a go-pbrt checkout, where there is one
 # cgo pseudo-identifiers and C scalar types, not ABI names
 CGO_BUILTINS = {"GoString", "CString", "GoBytes", "int", "int32_t", "int64_t", "uint8_t", "double", "size_t",
                 "uint64_t", "float", "char", "int32_t", "malloc", "free"}
@@ -82,18 +83,88 @@ def test_dropin_types_cover_the_reference_interfaces():
         assert f"func (r *Recorder) {ctor}(" in src, ctor
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE) or not os.path.exists("/usr/bin/patch"),
-                    reason="the reference checkout (or patch(1)) is not on this machine")
+def _sha(lines):
+    return hashlib.sha256("".join(l + "\n" for l in lines).encode()).hexdigest()
+
+
+def patch_hunks(path):
+    """The hunks of a unified diff: (target, creates, old_start, old_count,
+    old_lines, new_start, new_count, new_lines); target is the -p1 path,
+    creates says that the patch adds the file (its old side is /dev/null)."""
+    out, old, new, target, creates = [], None, None, None, False
+    for line in open(path).read().split("\n"):
+        if line.startswith("--- "):
+            creates = line[4:].split("\t")[0] == "/dev/null"
+        elif line.startswith("+++ "):
+            target = line[4:].split("\t")[0].split("/", 1)[1]
+        elif line.startswith("@@ "):
+            m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+            o0, on, n0, nn = (int(g) if g is not None else 1 for g in m.groups())
+            old, new = [], []
+            out.append((target, creates, o0, on, old, n0, nn, new))
+        elif old is not None and line[:1] in (" ", "-", "+"):
+            if line[0] != "+":
+                old.append(line[1:])
+            if line[0] != "-":
+                new.append(line[1:])
+    return out
+
+
+def record_targets(reference):
+    """What the patches need of the reference checkout, as recorded in
+    tests/golden/reference_patch_targets.json: per target file its line count
+    and SHA-256, and the SHA-256 of the lines each hunk replaces, read from the
+    checkout at the hunk's own position (so a hunk that needs an offset or
+    fuzz does not match). Hashes only: none of the reference's text."""
+    rec = {}
+    for f in sorted(os.listdir(PATCHES)):
+        for target, creates, o0, on, _, _, _, _ in patch_hunks(os.path.join(PATCHES, f)):
+            p = os.path.join(reference, target)
+            if creates or not os.path.exists(p):
+                rec[target] = {"exists": os.path.exists(p)}
+                continue
+            raw = open(p, "rb").read()
+            lines = raw.decode().split("\n")[:-1]
+            t = rec.setdefault(target, {"exists": True, "lines": len(lines),
+                                        "sha256": hashlib.sha256(raw).hexdigest(), "hunks": {}})
+            t["hunks"][str(o0)] = {"count": on, "sha256": _sha(lines[o0 - 1:o0 - 1 + on])}
+    return rec
+
+
 def test_patches_apply_to_the_reference(tmp_path):
-    """integration/go/patches/*.patch apply cleanly to the reference checkout
-    (dry run: nothing under /root/reference is written), and the hook patch puts
-    the FrameRenderer check at the top of pbrt.Render (integrator.go:291)."""
+    """integration/go/patches/*.patch apply cleanly to the reference checkout,
+    and the hook patch puts the FrameRenderer check at the top of pbrt.Render
+    (integrator.go:291). The checkout is not part of this repository: what the
+    patches need of it is recorded in tests/golden/reference_patch_targets.json
+    (record_targets), and every hunk's old side must be exactly the recorded
+    lines at the hunk's position, with no offset and no fuzz. Where
+    GO_PBRT_REFERENCE names a checkout, the record is checked against it and
+    patch(1) does a dry run on it (nothing is written there)."""
     pats = sorted(f for f in os.listdir(PATCHES) if f.endswith(".patch"))
     assert len(pats) == 2
+    rec = json.load(open(os.path.join(REPO, "tests", "golden", "reference_patch_targets.json")))
+    seen = set()
     for f in pats:
-        r = subprocess.run(["patch", "--dry-run", "-p1", "-d", REFERENCE, "-i", os.path.join(PATCHES, f)],
-                           capture_output=True, text=True)
-        assert r.returncode == 0, r.stdout + r.stderr
+        end = {}
+        for target, creates, o0, on, old, n0, nn, new in patch_hunks(os.path.join(PATCHES, f)):
+            assert len(old) == on and len(new) == nn, (f, target, o0)
+            t = rec[target]
+            if creates:
+                assert not t["exists"] and (o0, on) == (0, 0), (f, target)
+                continue
+            h = t["hunks"][str(o0)]
+            assert t["exists"] and h["count"] == on and h["sha256"] == _sha(old), (f, target, o0)
+            assert end.get(target, 0) < o0 and o0 + on - 1 <= t["lines"], (f, target, o0)   # ascending, inside
+            end[target] = o0 + on - 1
+            seen.add((target, str(o0)))
+    assert seen == {(t, k) for t, v in rec.items() for k in v.get("hunks", {})}
+    if REFERENCE and os.path.isdir(REFERENCE):
+        assert record_targets(REFERENCE) == rec
+        if shutil.which("patch"):
+            for f in pats:
+                r = subprocess.run(["patch", "--dry-run", "-p1", "-d", REFERENCE, "-i", os.path.join(PATCHES, f)],
+                                   capture_output=True, text=True)
+                assert r.returncode == 0, r.stdout + r.stderr
     hook = open(os.path.join(PATCHES, pats[0])).read()
     assert "+\tif fr, ok := s.(FrameRenderer); ok {" in hook and "+func RenderTiles(" in hook
     server = open(os.path.join(PATCHES, pats[1])).read()
@@ -116,3 +187,11 @@ def test_batch_arrays_live_in_c_memory():
     rf = shim[shim.index("func (r *Renderer) RenderFrame("):]
     rf = rf[:rf.index("\n}\n")]
     assert "<-exited" in rf and rf.index("close(done)") < rf.index("<-exited") < rf.index("switch rc")
+
+
+if __name__ == "__main__":   # python tests/test_go_shim.py <go-pbrt checkout>: rewrite the record
+    import sys
+
+    with open(os.path.join(REPO, "tests", "golden", "reference_patch_targets.json"), "w") as out:
+        json.dump(record_targets(sys.argv[1]), out, indent=1, sort_keys=True)
+        out.write("\n")

@@ -69,3 +69,35 @@ def test_kernel_resources_parser(tmp_path):
     assert v == {"arch_vgpr": 200, "acc_vgpr": 0, "sgpr": 100, "scratch_bytes_per_lane": 28,
                  "lds_static_bytes": 6640, "waves_per_simd_by_registers": 2}
     out_file.write_text(buf.getvalue())
+
+
+def test_bench_plain_run_has_no_extra_legs_by_default(monkeypatch):
+    """bench.py's side mode, per-request leg and CPU baseline run only under --full."""
+    bench = _load(os.path.join(REPO, "bench.py"), "bench_for_test")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, "", 4, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "d" and not (a.no_cpu_baseline or a.no_side_mode or a.no_rpc)
+
+
+def test_bench_dump_outputs_whole_film_and_fixed_sample(tmp_path, monkeypatch):
+    """--dump-outputs: film.npy is the float64 film itself while it fits the
+    byte budget, and otherwise the same seeded, ascending pixel sample of it in
+    every run."""
+    import torch
+
+    bench = _load(os.path.join(REPO, "bench.py"), "bench_for_test")
+    film = torch.arange(7 * 5 * 3, dtype=torch.float64).reshape(7, 5, 3)
+    bench.dump_outputs(str(tmp_path / "a"), film)
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, film.numpy())
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 10 * 24 + 5)   # room for 10 of the 35 pixels
+    bench.dump_outputs(str(tmp_path / "b"), film)
+    bench.dump_outputs(str(tmp_path / "c"), film)
+    s = np.load(tmp_path / "b" / "film.npy")
+    assert s.dtype == np.float64 and s.shape == (10, 3) and s.nbytes <= bench.DUMP_MAX_BYTES
+    assert np.array_equal(s, np.load(tmp_path / "c" / "film.npy"))
+    pix = (s[:, 0] // 3).astype(int)   # a pixel's first channel holds 3 * its row-major index
+    assert np.all(np.diff(pix) > 0) and np.array_equal(s, film.numpy().reshape(35, 3)[pix])

@@ -14,11 +14,11 @@ tests)
 profile)
   bash tools/profile_round.sh ${TAG}_B ;;
 benches)
-  timeout -k 10 300 python bench.py --config C --steps 1 > $OUT/bench_C.json 2> $OUT/bench_C.err &&
+  timeout -k 10 300 python bench.py --full --config C --steps 1 > $OUT/bench_C.json 2> $OUT/bench_C.err &&
   echo "C done" &&
-  timeout -k 10 300 python bench.py --config D --steps 2 > $OUT/bench_D.json 2> $OUT/bench_D.err &&
+  timeout -k 10 300 python bench.py --full --config D --steps 2 > $OUT/bench_D.json 2> $OUT/bench_D.err &&
   echo "D done" &&
-  timeout -k 10 500 python bench.py --config E --shard 0/8 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_E.json 2> $OUT/bench_E.err &&
+  timeout -k 10 500 python bench.py --full --config E --shard 0/8 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_E.json 2> $OUT/bench_E.err &&
   echo "E done" ;;
 *) echo "usage: $0 <tag> tests|profile|benches"; exit 2 ;;
 esac

@@ -34,7 +34,7 @@ for step in "$@"; do
     timeout -k 10 500 python bench.py --config $cfg --no-cpu-baseline --no-side-mode --no-rpc $extra > $OUT/bench_$cfg.json 2> $OUT/bench_$cfg.err || { echo "bench $cfg failed"; tail -20 $OUT/bench_$cfg.err; exit 1; } ;;
   benchfull=*)
     cfg=${step#benchfull=}
-    timeout -k 10 600 python bench.py --config $cfg > $OUT/benchfull_$cfg.json 2> $OUT/benchfull_$cfg.err || { echo "bench $cfg failed"; tail -20 $OUT/benchfull_$cfg.err; exit 1; } ;;
+    timeout -k 10 600 python bench.py --full --config $cfg > $OUT/benchfull_$cfg.json 2> $OUT/benchfull_$cfg.err || { echo "bench $cfg failed"; tail -20 $OUT/benchfull_$cfg.err; exit 1; } ;;
   profile=*)
     cfg=${step#profile=}
     bash tools/profile_round.sh ${TAG}/prof_$cfg --config $cfg || { echo "profile $cfg failed"; exit 1; } ;;
