@@ -1870,6 +1870,15 @@ void pbrt_gpu_destroy(pbrt_gpu_ctx* c) {
     delete c;
 }
 
+}  // extern "C"
+
+// what a device group (group.hip) reads of a member after its frame
+pbrtk::GroupMemberView pbrt_group_member_view(const pbrt_gpu_ctx* c) {
+    return pbrtk::GroupMemberView{c->device, c->d_films, c->d_film, &c->host_scene.film, c->rp};
+}
+
+extern "C" {
+
 // film.go:142-179 WriteImage pixel conversion
 int pbrt_film_to_rgba8(const double* film, int64_t w, int64_t h, uint8_t* rgba) {
     if (!film || !rgba || w <= 0 || h <= 0) return PBRT_E_INVALID;

@@ -13,4 +13,6 @@
 #include "k_serial.hip"
 #include "k_pw.hip"
 #include "k_frame.hip"
+#include "k_group.hip"
 #include "render.hip"
+#include "group.hip"

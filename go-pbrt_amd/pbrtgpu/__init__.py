@@ -64,6 +64,7 @@ def lib():
     L.pbrt_gpu_last_error.restype = C.c_char_p
     L.pbrt_gpu_destroy.argtypes = [C.c_void_p]
     L.pbrt_gpu_destroy.restype = None
+    abi.declare_group(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
     L.pbrt_gpu_tile_ticks.argtypes = [C.c_void_p, P(C.c_uint32), i64, P(i64)]
     L.pbrt_gpu_tile_ticks.restype = i64
@@ -505,6 +506,90 @@ class Renderer:
     def close(self):
         if getattr(self, "h", None):
             lib().pbrt_gpu_destroy(self.h)
+            self.h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        self.close()
+
+
+class RendererGroup:
+    """pbrt_gpu_group: the scene resident on several GPUs, rendered as one frame.
+
+    devices: 1..8 HIP ordinals (one member each; an ordinal may repeat, which
+    runs the whole mechanism on one GPU). The film is merged on devices[0] in
+    tile-index order and is bit-identical to a single Renderer's."""
+
+    def __init__(self, scene, devices, lanes_per_wave=0, occupancy=0, kernel="auto"):
+        desc = scene.desc if isinstance(scene, Scene) else scene
+        self._scene = scene  # keep the descriptor alive
+        opts = abi.GpuOpts()
+        opts.device, opts.lanes_per_wave = -1, lanes_per_wave
+        opts.occupancy, opts.kernel = occupancy, Renderer.KERNELS[kernel]
+        devices = list(devices)
+        devs = (C.c_int32 * max(len(devices), 1))(*devices)
+        h = C.c_void_p()
+        rc = lib().pbrt_gpu_group_create(C.byref(desc), C.byref(opts), devs, len(devices), C.byref(h))
+        if rc:
+            raise PbrtError(rc, "pbrt_gpu_group_create failed (bad device list, or no GPU visible?)")
+        self.h = h.value
+        self.devices = devices
+        self.w = desc.film.crop_max_x - desc.film.crop_min_x
+        self.hgt = desc.film.crop_max_y - desc.film.crop_min_y
+
+    def _check(self, rc, stats=None):
+        if rc:
+            raise PbrtError(rc, lib().pbrt_gpu_group_last_error(self.h).decode(), stats)
+
+    def __len__(self):
+        return lib().pbrt_gpu_group_size(self.h)
+
+    def render(self, rd):
+        film = np.zeros((self.hgt, self.w, 3), dtype=np.float64)
+        st = abi.GpuStats()
+        rc = lib().pbrt_gpu_group_render(self.h, C.byref(rd), film.ctypes.data_as(C.POINTER(C.c_double)), C.byref(st))
+        self._check(rc, st)
+        return film, st
+
+    def render_async(self, rd, film_device_ptr=None):
+        """Start a frame; film_device_ptr = caller buffer on devices[0] (e.g. tensor.data_ptr())."""
+        self._check(lib().pbrt_gpu_group_render_async(self.h, C.byref(rd),
+                                                      C.c_void_p(film_device_ptr) if film_device_ptr else None))
+
+    def synchronize(self):
+        st = abi.GpuStats()
+        self._check(lib().pbrt_gpu_group_synchronize(self.h, C.byref(st)), st)
+        return st
+
+    def film(self):
+        film = np.zeros((self.hgt, self.w, 3), dtype=np.float64)
+        self._check(lib().pbrt_gpu_group_film_download(self.h, film.ctypes.data_as(C.POINTER(C.c_double))))
+        return film
+
+    def film_device_ptr(self):
+        return lib().pbrt_gpu_group_film_device(self.h)
+
+    def member_stats(self, i):
+        st = abi.GpuStats()
+        self._check(lib().pbrt_gpu_group_member_stats(self.h, i, C.byref(st)))
+        return st
+
+    def member_schedule_source(self, i):
+        """PBRT_SCHED_* of member i's last EXACT frame (pbrt_gpu_schedule_source)."""
+        return lib().pbrt_gpu_schedule_source(lib().pbrt_gpu_group_member(self.h, i))
+
+    def cancel(self):
+        """Cancel the frame in flight on every member (thread-safe)."""
+        lib().pbrt_gpu_group_cancel(self.h)
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().pbrt_gpu_group_destroy(self.h)
             self.h = None
 
     def __enter__(self):

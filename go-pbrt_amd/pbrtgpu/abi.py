@@ -280,3 +280,28 @@ def render_desc(spp_x=8, spp_y=8, jitter=False, n_dims=4, integrator=PBRT_INTEGR
     rd.tile_size, rd.tile_begin, rd.tile_end, rd.tile_stride = tile_size, tile_begin, tile_end, tile_stride
     rd.mode, rd.flags = mode, flags
     return rd
+
+
+PBRT_GROUP_MAX = 8
+
+
+def declare_group(L):
+    """ctypes prototypes of the device-group entry points (pbrt_gpu_group_*)."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_group_create.argtypes = [P(SceneDesc), P(GpuOpts), P(C.c_int32), C.c_int32, P(vp)]
+    L.pbrt_gpu_group_render.argtypes = [vp, P(RenderDesc), P(C.c_double), P(GpuStats)]
+    L.pbrt_gpu_group_render_async.argtypes = [vp, P(RenderDesc), vp]
+    L.pbrt_gpu_group_synchronize.argtypes = [vp, P(GpuStats)]
+    L.pbrt_gpu_group_film_device.argtypes = [vp]
+    L.pbrt_gpu_group_film_device.restype = vp
+    L.pbrt_gpu_group_film_download.argtypes = [vp, P(C.c_double)]
+    L.pbrt_gpu_group_size.argtypes = [vp]
+    L.pbrt_gpu_group_member.argtypes = [vp, C.c_int]
+    L.pbrt_gpu_group_member.restype = vp
+    L.pbrt_gpu_group_member_stats.argtypes = [vp, C.c_int, P(GpuStats)]
+    L.pbrt_gpu_group_cancel.argtypes = [vp]
+    L.pbrt_gpu_group_cancel.restype = None
+    L.pbrt_gpu_group_last_error.argtypes = [vp]
+    L.pbrt_gpu_group_last_error.restype = C.c_char_p
+    L.pbrt_gpu_group_destroy.argtypes = [vp]
+    L.pbrt_gpu_group_destroy.restype = None

@@ -40,7 +40,8 @@ typedef enum pbrt_status {
     PBRT_OK = 0,
     PBRT_E_INVALID = 1,      /* bad descriptor / argument                     */
     PBRT_E_HIP = 2,          /* HIP runtime failure                           */
-    PBRT_E_RCCL = 3,         /* collective failure (multi-GPU film reduce)    */
+    PBRT_E_RCCL = 3,         /* reserved: the library links no collective; a
+                                device group merges over peer access        */
     PBRT_E_CANCELLED = 4,    /* pbrt_gpu_cancel() observed                    */
     PBRT_E_REF_PANIC = 5,    /* the Go reference would have panicked here     */
     PBRT_E_UNSUPPORTED = 6   /* descriptor uses a feature not on the hot path */
@@ -335,7 +336,8 @@ int pbrt_gpu_render(pbrt_gpu_ctx* ctx, const pbrt_render_desc* rd,
  * not synchronize with the host: the bench's timed region. */
 int pbrt_gpu_render_async(pbrt_gpu_ctx* ctx, const pbrt_render_desc* rd);
 /* Same, merging the film into a caller-owned device buffer of res_x*res_y*3
- * doubles (e.g. a torch tensor that is then reduced over RCCL). */
+ * doubles (e.g. a torch tensor's storage). For one frame over several GPUs
+ * see pbrt_gpu_group below. */
 int pbrt_gpu_render_async_into(pbrt_gpu_ctx* ctx, const pbrt_render_desc* rd, double* film_device);
 int pbrt_gpu_synchronize(pbrt_gpu_ctx* ctx, pbrt_gpu_stats* stats);
 /* device pointer to the res_x*res_y*3 fp64 film of the last render */
@@ -363,6 +365,56 @@ int pbrt_gpu_intersect_p(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, size_t n,
 void pbrt_gpu_cancel(pbrt_gpu_ctx* ctx);
 const char* pbrt_gpu_last_error(const pbrt_gpu_ctx* ctx);
 void pbrt_gpu_destroy(pbrt_gpu_ctx* ctx);
+
+/* ------------------------------------------------------------ device groups */
+/* One scene resident on several GPUs, rendered as one frame. The group splits
+ * the tiles rd names over its members (the k-th of them goes to member k mod N),
+ * every member renders its share through the single-context path, and one
+ * kernel on the leader (member 0) reads all members' tile films -- over peer
+ * access, or from a staging copy on the leader where peer access is refused
+ * or PBRT_GROUP_STAGE=1 is set when the group is created -- and adds them in
+ * tile-index order, as Film.MergeFilmTile does. The film is therefore
+ * bit-identical to the one a single context renders, whatever the member
+ * count; a sum of per-shard films is not (it adds in shard order).
+ *
+ * devices holds 1..PBRT_GROUP_MAX HIP ordinals. An ordinal MAY REPEAT:
+ * {0, 0, 0} is three members on one GPU. Members that share a GPU render one
+ * after the other, so repeats bring no speed; they exist so that the whole
+ * mechanism can be exercised on a machine with one GPU. opts->device is
+ * ignored. A NULL scene, devices or out, n_devices outside 1..PBRT_GROUP_MAX
+ * or a negative ordinal is PBRT_E_INVALID before any device call.
+ *
+ * The calls mirror the context's. render_async starts the frame and returns;
+ * errors of the frame (a bad render desc included) are reported by
+ * synchronize, which waits for every member, then merges. film_device, when
+ * not NULL, is a caller-owned buffer of res_x*res_y*3 doubles on the leader's
+ * device. Stats: counts are summed over the members; kernel_ms, chain_ms,
+ * paths_ms and batches are the maximum over them; merge_ms is the device time
+ * of the group merge (staging copies included); total_ms is host wall time. A
+ * reference panic is reported for the lowest panicking tile over all members
+ * and no film is merged. cancel cancels every member: the frame's synchronize
+ * returns PBRT_E_CANCELLED without merging, the next frame runs normally. A
+ * group serves one frame at a time, from one thread; only cancel may be
+ * called from another. */
+typedef struct pbrt_gpu_group pbrt_gpu_group;
+#define PBRT_GROUP_MAX 8
+int pbrt_gpu_group_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts,
+                          const int32_t* devices, int32_t n_devices, pbrt_gpu_group** out);
+int pbrt_gpu_group_render(pbrt_gpu_group* g, const pbrt_render_desc* rd, double* film_xyz,
+                          pbrt_gpu_stats* stats);
+int pbrt_gpu_group_render_async(pbrt_gpu_group* g, const pbrt_render_desc* rd, double* film_device);
+int pbrt_gpu_group_synchronize(pbrt_gpu_group* g, pbrt_gpu_stats* stats);
+/* device pointer (on the leader) to the film of the last frame */
+double* pbrt_gpu_group_film_device(pbrt_gpu_group* g);
+int pbrt_gpu_group_film_download(pbrt_gpu_group* g, double* film_xyz);
+int pbrt_gpu_group_size(const pbrt_gpu_group* g);
+/* diagnostics: member i's context (schedule source, counters) and its stats of
+ * the last frame. Do not render on or destroy a member. */
+pbrt_gpu_ctx* pbrt_gpu_group_member(pbrt_gpu_group* g, int i);
+int pbrt_gpu_group_member_stats(pbrt_gpu_group* g, int i, pbrt_gpu_stats* stats);
+void pbrt_gpu_group_cancel(pbrt_gpu_group* g);
+const char* pbrt_gpu_group_last_error(const pbrt_gpu_group* g);
+void pbrt_gpu_group_destroy(pbrt_gpu_group* g);
 
 /* PNG-byte conversion of film.go:142-179 WriteImage: uint8(clamp(XYZ,0,1)*255),
  * no XYZ->RGB and no gamma, exactly as the reference. rgba: w*h*4 bytes. */

@@ -301,25 +301,34 @@ func (r *Recorder) build() error {
 type Path struct {
 	pbrt.Integrator // the CPU integrator.Path: Li, Preprocess, GetSampler, GetCamera, Specular*
 
-	rec    *Recorder
-	rd     C.pbrt_render_desc
-	device int
+	rec     *Recorder
+	rd      C.pbrt_render_desc
+	devices []int
 
 	once     sync.Once
-	renderer *Renderer
+	renderer frameRenderer
 	err      error
 }
 
+// frameRenderer is what Path needs of a Renderer or a RendererGroup.
+type frameRenderer interface {
+	RenderFrame(ctx context.Context, rd *C.pbrt_render_desc, film []float64) error
+	Close()
+}
+
 // NewPath is integrator.NewPath(maxDepth, camera, sampler, pixelBounds,
-// rrThreshold, strategy); device is the HIP ordinal the frame renders on.
+// rrThreshold, strategy); devices are the HIP ordinals the frame renders on:
+// one is a Renderer, more a RendererGroup, which splits the frame's tiles over
+// them and merges the same film bit for bit. An empty list is an error, which
+// RenderFrame returns.
 func (r *Recorder) NewPath(maxDepth int32, camera pbrt.Camera, smp *Stratified, pixelBounds *pbrt.Bounds2i,
-	rrThreshold float64, strategy pbrt.LightSampleStrategy, device int) *Path {
+	rrThreshold float64, strategy pbrt.LightSampleStrategy, devices ...int) *Path {
 	rd := PathDesc(smp.X, smp.Y, smp.Jitter, int32(smp.NDims), maxDepth, rrThreshold, int32(strategy))
 	return &Path{
 		Integrator: integrator.NewPath(maxDepth, camera, smp, pixelBounds, rrThreshold, strategy),
 		rec:        r,
 		rd:         rd,
-		device:     device,
+		devices:    devices,
 	}
 }
 
@@ -332,7 +341,25 @@ func (p *Path) RenderFrame(ctx context.Context, scene pbrt.Scene, tileSize int64
 	if err := p.rec.build(); err != nil {
 		return pbrt.RenderTiles(ctx, p, scene, tileSize)
 	}
-	p.once.Do(func() { p.renderer, p.err = NewRenderer(p.rec.sb, p.device) })
+	p.once.Do(func() {
+		// assign through the concrete types: a nil *Renderer in the interface would not be nil
+		switch len(p.devices) {
+		case 0:
+			p.err = errors.New("pbrtgpu: NewPath was given no device")
+		case 1:
+			if r, err := NewRenderer(p.rec.sb, p.devices[0]); err != nil {
+				p.err = err
+			} else {
+				p.renderer = r
+			}
+		default:
+			if g, err := NewRendererGroup(p.rec.sb, p.devices); err != nil {
+				p.err = err
+			} else {
+				p.renderer = g
+			}
+		}
+	})
 	if p.err != nil {
 		return p.err
 	}

@@ -292,6 +292,93 @@ func (r *Renderer) IntersectP(rays *C.pbrt_ray_soa, n int, occluded []uint8) err
 
 func (r *Renderer) Close() { C.pbrt_gpu_destroy(r.ctx) }
 
+// RendererGroup owns the scene resident on several GPUs (pbrt_gpu_group): the
+// frame's tiles are split over the devices and merged on the first of them in
+// tile-index order, so the film is bit-identical to a single Renderer's.
+type RendererGroup struct {
+	g    *C.pbrt_gpu_group
+	w, h int
+}
+
+// NewRendererGroup creates one member per entry of devices (HIP ordinals, 1..8
+// of them; an ordinal may repeat, which only serves tests on one GPU).
+func NewRendererGroup(s *SceneBuilder, devices []int) (*RendererGroup, error) {
+	if s.desc == nil {
+		return nil, fmt.Errorf("pbrtgpu: scene not built")
+	}
+	if len(devices) == 0 || len(devices) > C.PBRT_GROUP_MAX {
+		return nil, fmt.Errorf("pbrtgpu: a group has 1..%d devices, got %d", int(C.PBRT_GROUP_MAX), len(devices))
+	}
+	devs := make([]C.int32_t, len(devices))
+	for i, d := range devices {
+		devs[i] = C.int32_t(d)
+	}
+	var opts C.pbrt_gpu_opts
+	var g *C.pbrt_gpu_group
+	if rc := C.pbrt_gpu_group_create(s.desc, &opts, &devs[0], C.int32_t(len(devs)), &g); rc != C.PBRT_OK {
+		return nil, fmt.Errorf("pbrt_gpu_group_create: status %d", int(rc))
+	}
+	f := s.desc.film
+	return &RendererGroup{g: g, w: int(f.crop_max_x - f.crop_min_x), h: int(f.crop_max_y - f.crop_min_y)}, nil
+}
+
+// Size is the number of members.
+func (r *RendererGroup) Size() int { return int(C.pbrt_gpu_group_size(r.g)) }
+
+// RenderFrame is Renderer.RenderFrame over the group: same film, same
+// cancellation (ctx maps to pbrt_gpu_group_cancel, which cancels every member)
+// and the same panic contract (the lowest panicking tile over all members).
+func (r *RendererGroup) RenderFrame(ctx context.Context, rd *C.pbrt_render_desc, film []float64) error {
+	if len(film) < r.w*r.h*3 || len(film) == 0 {
+		return fmt.Errorf("pbrtgpu: film holds %d values, the frame needs %d", len(film), r.w*r.h*3)
+	}
+	if err := ctx.Err(); err != nil {
+		return err
+	}
+	// as in Renderer.RenderFrame: the watcher is joined before returning, so no
+	// cancel can reach the group after the caller's Close
+	done := make(chan struct{})
+	exited := make(chan struct{})
+	go func() {
+		defer close(exited)
+		select {
+		case <-ctx.Done():
+			C.pbrt_gpu_group_cancel(r.g)
+		case <-done:
+		}
+	}()
+	var st C.pbrt_gpu_stats
+	rc := C.pbrt_gpu_group_render(r.g, rd, (*C.double)(unsafe.Pointer(&film[0])), &st)
+	close(done)
+	<-exited
+	switch rc {
+	case C.PBRT_OK:
+		return nil
+	case C.PBRT_E_CANCELLED:
+		if err := ctx.Err(); err != nil {
+			return err
+		}
+		return context.Canceled
+	case C.PBRT_E_REF_PANIC: // the CPU reference panics here; keep that contract
+		panic(fmt.Sprintf("go-pbrt panic kind %d at tile %d pixel (%d,%d) sample %d bounce %d",
+			int(st.panic_kind), int(st.panic_tile), int64(st.panic_pixel_x), int64(st.panic_pixel_y),
+			int(st.panic_sample), int(st.panic_bounce)))
+	default:
+		return fmt.Errorf("pbrt_gpu_group_render: %s", C.GoString(C.pbrt_gpu_group_last_error(r.g)))
+	}
+}
+
+// MemberStats is member i's pbrt_gpu_stats of the last frame.
+func (r *RendererGroup) MemberStats(i int) (C.pbrt_gpu_stats, error) {
+	var st C.pbrt_gpu_stats
+	if rc := C.pbrt_gpu_group_member_stats(r.g, C.int(i), &st); rc != C.PBRT_OK {
+		return st, fmt.Errorf("pbrt_gpu_group_member_stats: status %d", int(rc))
+	}
+	return st, nil
+}
+
+func (r *RendererGroup) Close() { C.pbrt_gpu_group_destroy(r.g) }
+
 // FilmToRGBA is Film.WriteImage's pixel loop (film.go:156-161): uint8(Clamp(v, 0, 1) * 255)
 // of the XYZ sums, NaN -> 0, alpha 255; encode the result with image/png as WriteImage does.
 func FilmToRGBA(film []float64, w, h int) (*image.RGBA, error) {
