@@ -138,6 +138,36 @@ def lib():
     return L
 
 
+def hip_runtimes():
+    """Paths of the distinct HIP runtime libraries (libamdhip64) mapped into this
+    process. One is normal. Two means that a torch wheel's own copy and the one
+    libpbrt_gpu.so links were both loaded, which happens when the library is
+    loaded before torch is imported; the copy that
+    initialises second then finds no GPU."""
+    found = []
+    try:
+        with open("/proc/self/maps") as maps:
+            for line in maps:
+                part = line.split(None, 5)
+                if len(part) == 6 and "libamdhip64" in os.path.basename(part[5].strip()):
+                    path = part[5].strip()
+                    if path not in found:
+                        found.append(path)
+    except OSError:   # no procfs: nothing to report
+        pass
+    return found
+
+
+def _create_failed(what):
+    """The message of a failed pbrt_gpu[_group]_create."""
+    rts = hip_runtimes()
+    if len(rts) > 1:
+        return (f"{what} failed: this process holds {len(rts)} HIP runtimes ({', '.join(rts)}) and only the "
+                "first to initialise sees the GPU; import torch before pbrtgpu loads libpbrt_gpu.so "
+                "(pbrtgpu.lib(), a Scene or a Renderer) so that both share one")
+    return f"{what} failed (no GPU visible?)"
+
+
 def build_id():
     """Content hash of the sources the loaded library was built from."""
     return lib().pbrt_gpu_build_id().decode()
@@ -371,7 +401,8 @@ class Renderer:
         h = C.c_void_p()
         rc = lib().pbrt_gpu_create(C.byref(desc), C.byref(opts), C.byref(h))
         if rc:
-            raise PbrtError(rc, "pbrt_gpu_create failed (no GPU visible?)")
+            raise PbrtError(rc, _create_failed("pbrt_gpu_create") if rc == abi.PBRT_E_HIP
+                            else "pbrt_gpu_create failed (bad scene descriptor or options)")
         self.h = h.value
         self.w = desc.film.crop_max_x - desc.film.crop_min_x
         self.hgt = desc.film.crop_max_y - desc.film.crop_min_y
@@ -536,7 +567,8 @@ class RendererGroup:
         h = C.c_void_p()
         rc = lib().pbrt_gpu_group_create(C.byref(desc), C.byref(opts), devs, len(devices), C.byref(h))
         if rc:
-            raise PbrtError(rc, "pbrt_gpu_group_create failed (bad device list, or no GPU visible?)")
+            raise PbrtError(rc, _create_failed("pbrt_gpu_group_create") if rc == abi.PBRT_E_HIP
+                            else "pbrt_gpu_group_create failed (bad device list, scene descriptor or options)")
         self.h = h.value
         self.devices = devices
         self.w = desc.film.crop_max_x - desc.film.crop_min_x
