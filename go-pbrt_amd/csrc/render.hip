@@ -17,6 +17,8 @@
 //   k_merge_film     Film.MergeFilmTile (film.go:115-132): per output pixel,
 //                    RGBToXYZ of every covering tile film in tile-index order.
 //   k_intersect[_p]  batch BVH closest-hit / any-hit (bvh.go:659-765).
+//   k_query_*        the same over SoA arrays resident on the device, and the
+//                    camera rays of a pixel window (pbrt_gpu_*_device).
 //
 // Everything is float64 with -ffp-contract=off (bit parity with the Go
 // reference). The scene is a few KB and is read through the scalar/vector L1.
@@ -39,6 +41,7 @@
 #include "../../include/pbrt_diag.h"
 #include "../../include/pbrt_scene.h"
 #include "mesh_bvh.h"
+#include "query_buffers.h"
 #include "render_kernels.h"
 
 using namespace pbrt;
@@ -261,6 +264,11 @@ struct pbrt_gpu_ctx {
     int* h_cancel = nullptr;   // hipHostMalloc (coherent, mapped)
     int* d_cancel = nullptr;   // its device address
     int* d_cancel_seen = nullptr;   // device-memory copy the kernels publish (reset per render)
+    // device-resident queries: the buffers the context owns (pbrt_gpu_buffer;
+    // whatever is left is freed by pbrt_gpu_destroy) and the panic record of
+    // the queries since the last pbrt_gpu_query_status (allocated by the first)
+    pbrtq::BufferList qbufs;
+    QueryRec* d_qrec = nullptr;
     std::string err;
     std::chrono::steady_clock::time_point t_start;
 };
@@ -1828,6 +1836,147 @@ int pbrt_gpu_intersect_p(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, ui
     return intersect_batch(c, rays, n, 1, nullptr, occluded);
 }
 
+// ------------------------------------------------ device-resident queries
+// A query may go on the stream only between frames: a frame in flight owns the
+// context's counters and buffers, and its kernels may be waiting on one another
+// across the context's streams.
+static bool query_blocked(pbrt_gpu_ctx* c) {
+    std::lock_guard<std::mutex> lk(c->cancel_mu);
+    return c->in_flight;
+}
+// the record cleared, in stream order (so after the queries already enqueued)
+static hipError_t query_rec_clear(pbrt_gpu_ctx* c) {
+    hipError_t e = hipMemsetAsync(&c->d_qrec->panics, 0, sizeof(c->d_qrec->panics), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(&c->d_qrec->first, 0xFF, sizeof(c->d_qrec->first), c->stream);
+    return e;
+}
+// the one allocation of the query path, on a context's first query
+static int query_rec_ensure(pbrt_gpu_ctx* c) {
+    if (c->d_qrec) return PBRT_OK;
+    HIPCHK(c, hipMalloc((void**)&c->d_qrec, sizeof(QueryRec)));
+    HIPCHK(c, query_rec_clear(c));
+    return PBRT_OK;
+}
+
+static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool any, const pbrt_hit_soa& hits) {
+    if (!c || !rays || !hits.hit) return PBRT_E_INVALID;
+    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz)
+        return set_err(c, PBRT_E_INVALID, "a ray array is NULL");
+    if (n > (size_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
+    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = query_rec_ensure(c)) return rc;
+    const DevScene sc = with_slot(dev_scene(c, false), 7);
+    const dim3 grid((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
+    const bool mesh_only = c->host_scene.n_prims == 0;   // as the render path chooses its kMeshOnly kernels
+#define PBRT_QUERY_LAUNCH(A, M) \
+    hipLaunchKernelGGL((k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec)
+    if (any) {
+        if (mesh_only) PBRT_QUERY_LAUNCH(true, true);
+        else PBRT_QUERY_LAUNCH(true, false);
+    } else {
+        if (mesh_only) PBRT_QUERY_LAUNCH(false, true);
+        else PBRT_QUERY_LAUNCH(false, false);
+    }
+#undef PBRT_QUERY_LAUNCH
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+int pbrt_gpu_intersect_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, const pbrt_hit_soa* hits) {
+    if (!hits) return PBRT_E_INVALID;
+    return query_hit(c, rays, n, false, *hits);
+}
+int pbrt_gpu_intersect_p_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, uint8_t* occluded) {
+    pbrt_hit_soa h{};
+    h.hit = occluded;
+    return query_hit(c, rays, n, true, h);
+}
+
+int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d, const pbrt_ray_soa_out* rays) {
+    if (!c || !d || !rays) return PBRT_E_INVALID;
+    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz)
+        return set_err(c, PBRT_E_INVALID, "a ray array is NULL");
+    const pbrt_film_desc& f = c->host_scene.film;
+    if (d->x0 < 0 || d->x0 >= d->x1 || d->x1 > f.res_x || d->y0 < 0 || d->y0 >= d->y1 || d->y1 > f.res_y)
+        return set_err(c, PBRT_E_INVALID, "pixel window outside the film resolution");
+    const int64_t n = (d->x1 - d->x0) * (d->y1 - d->y0);
+    if (n > (int64_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
+    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    hipLaunchKernelGGL(k_query_camera, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0,
+                       c->stream, c->d_camera, *d, *rays);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+int pbrt_gpu_query_status(pbrt_gpu_ctx* c, pbrt_query_record* out) {
+    if (!c) return PBRT_E_INVALID;
+    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    QueryRec rec{0, ~0ull};
+    if (c->d_qrec) {
+        HIPCHK(c, hipMemcpy(&rec, c->d_qrec, sizeof(rec), hipMemcpyDeviceToHost));
+        if (rec.panics) HIPCHK(c, query_rec_clear(c));
+    }
+    if (out) {
+        out->panics = rec.panics;
+        out->first_ray = rec.panics ? (int64_t)(rec.first >> 8) : -1;
+        out->panic_kind = rec.panics ? (int32_t)(rec.first & 0xFF) : PBRT_PANIC_NONE;
+        out->pad0 = 0;
+    }
+    if (rec.panics) return set_err(c, PBRT_E_REF_PANIC, "the Go reference panics on at least one ray");
+    return PBRT_OK;
+}
+
+// ---- buffers the context owns (bookkeeping: query_buffers.h)
+int pbrt_gpu_buffer_create(pbrt_gpu_ctx* c, size_t bytes, pbrt_gpu_buffer** out) {
+    if (out) *out = nullptr;
+    if (!c || !out || bytes == 0) return PBRT_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    hipError_t e = hipSuccess;
+    pbrt_gpu_buffer* b = pbrtq::list_create(c->qbufs, c, bytes, [&e](size_t nb) {
+        void* p = nullptr;
+        e = hipMalloc(&p, nb);
+        return e == hipSuccess ? p : nullptr;
+    });
+    if (!b) return set_err(c, PBRT_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
+    *out = b;
+    return PBRT_OK;
+}
+void* pbrt_gpu_buffer_ptr(const pbrt_gpu_buffer* b) { return b ? b->ptr : nullptr; }
+size_t pbrt_gpu_buffer_size(const pbrt_gpu_buffer* b) { return b ? b->bytes : 0; }
+
+static int buffer_copy(pbrt_gpu_buffer* b, size_t offset, void* host, size_t bytes, bool up) {
+    if (!b || !b->ctx) return PBRT_E_INVALID;
+    pbrt_gpu_ctx* c = b->ctx;
+    if (!host && bytes) return set_err(c, PBRT_E_INVALID, "NULL host pointer");
+    if (!pbrtq::range_ok(b->bytes, offset, bytes)) return set_err(c, PBRT_E_INVALID, "range outside the buffer");
+    HIPCHK(c, hipSetDevice(c->device));
+    char* dev = (char*)b->ptr + offset;
+    if (bytes) {
+        if (up) HIPCHK(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
+        else HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return PBRT_OK;
+}
+int pbrt_gpu_buffer_upload(pbrt_gpu_buffer* b, size_t offset, const void* host, size_t bytes) {
+    return buffer_copy(b, offset, const_cast<void*>(host), bytes, true);
+}
+int pbrt_gpu_buffer_download(pbrt_gpu_buffer* b, size_t offset, void* host, size_t bytes) {
+    return buffer_copy(b, offset, host, bytes, false);
+}
+void pbrt_gpu_buffer_destroy(pbrt_gpu_buffer* b) {
+    if (!b || !b->ctx) return;
+    pbrt_gpu_ctx* c = b->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);   // no query still reads or writes it
+    pbrtq::list_destroy(c->qbufs, b, [](void* p) { (void)hipFree(p); });
+}
+
 void pbrt_gpu_cancel(pbrt_gpu_ctx* c) {
     if (!c) return;
     std::lock_guard<std::mutex> lk(c->cancel_mu);
@@ -1848,6 +1997,9 @@ void pbrt_gpu_destroy(pbrt_gpu_ctx* c) {
                     c->d_gmasks, c->d_cost,   c->d_cost_keys, c->d_pw, c->d_cancel_seen, c->d_prog};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
+    // the caller's buffers that are still alive (the streams are idle by now)
+    pbrtq::list_free_all(c->qbufs, [](void* p) { (void)hipFree(p); });
+    if (c->d_qrec) (void)hipFree(c->d_qrec);
     mesh_bvh_free(c->mesh);
     for (hipEvent_t e : c->bev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -62,6 +62,14 @@ struct Counters {
 };
 constexpr int kNumCounters = 6 + 8 + 64 + 3;
 
+// Device-resident queries (k_query.hip): threads per block, and the context's
+// panic record of the queries since the last pbrt_gpu_query_status.
+constexpr int kQueryBlock = 256;
+struct QueryRec {
+    unsigned long long panics;   // rays on which the reference panics (atomicAdd)
+    unsigned long long first;    // smallest (ray index << 8 | PBRT_PANIC_*) of them (atomicMin); ~0: none
+};
+
 __device__ __forceinline__ void tile_bounds(const RenderParams& rp, int64_t tile, int64_t& x0, int64_t& y0,
                                             int64_t& x1, int64_t& y1) {
     // integrator.go:316-325

@@ -14,5 +14,6 @@
 #include "k_pw.hip"
 #include "k_frame.hip"
 #include "k_group.hip"
+#include "k_query.hip"
 #include "render.hip"
 #include "group.hip"

@@ -65,6 +65,7 @@ def lib():
     L.pbrt_gpu_destroy.argtypes = [C.c_void_p]
     L.pbrt_gpu_destroy.restype = None
     abi.declare_group(L)
+    abi.declare_query(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
     L.pbrt_gpu_tile_ticks.argtypes = [C.c_void_p, P(C.c_uint32), i64, P(i64)]
     L.pbrt_gpu_tile_ticks.restype = i64
@@ -384,6 +385,130 @@ class Scene:
             self.h = None
 
 
+# --------------------------------------------------------------- device buffers
+class ContextToken:
+    """Whether a Renderer's context is alive. The Renderer and every DeviceBuffer
+    it made share one token, and Renderer.close() clears it before the context
+    is destroyed: from then on no buffer touches the library again, in whatever
+    order the objects are finalised (interpreter teardown included)."""
+    __slots__ = ("alive",)
+
+    def __init__(self):
+        self.alive = True
+
+
+BUFFER_DTYPES = (np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.uint8))
+RAY_KEYS = ("ox", "oy", "oz", "dx", "dy", "dz")
+HIT_DTYPES = {"hit": np.uint8, "t_max": np.float64, "prim": np.int32, "px": np.float64, "py": np.float64,
+              "pz": np.float64, "nx": np.float64, "ny": np.float64, "nz": np.float64}
+
+
+class DeviceBuffer:
+    """pbrt_gpu_buffer: n elements of float64, int32 or uint8 in device memory
+    that the Renderer's context owns. Made by Renderer.buffer / Renderer.upload.
+    It keeps its Renderer alive; once that Renderer is closed the buffer is
+    closed too (its memory went with the context): close() and deletion then do
+    nothing and every other use raises PbrtError."""
+
+    def __init__(self, renderer, handle, ptr, n, dtype):
+        self.renderer = renderer
+        self._token = renderer._token
+        self._h = handle
+        self._ptr = ptr
+        self.n = int(n)
+        self.dtype = np.dtype(dtype)
+
+    @property
+    def closed(self):
+        return self._h is None or not self._token.alive
+
+    def _live(self):
+        if self.closed:
+            raise PbrtError(abi.PBRT_E_INVALID, "the device buffer (or its Renderer) is closed")
+
+    @property
+    def ptr(self):
+        self._live()
+        return self._ptr
+
+    @property
+    def nbytes(self):
+        return self.n * self.dtype.itemsize
+
+    def upload(self, array, offset=0):
+        """Copies a host array to elements [offset, offset + len(array))."""
+        self._live()
+        a = np.ascontiguousarray(array)
+        if a.dtype != self.dtype:
+            raise PbrtError(abi.PBRT_E_INVALID, f"upload of {a.dtype} into a {self.dtype} buffer")
+        if offset < 0 or offset + a.size > self.n:
+            raise PbrtError(abi.PBRT_E_INVALID, f"elements [{offset}, {offset + a.size}) outside a buffer of {self.n}")
+        rc = lib().pbrt_gpu_buffer_upload(self._h, offset * self.dtype.itemsize, a.ctypes.data, a.nbytes)
+        self.renderer._check(rc)
+        return self
+
+    def download(self):
+        """The buffer's n elements as a host array (synchronises the context's stream)."""
+        self._live()
+        out = np.empty(self.n, dtype=self.dtype)
+        self.renderer._check(lib().pbrt_gpu_buffer_download(self._h, 0, out.ctypes.data, out.nbytes))
+        return out
+
+    def close(self):
+        h, self._h = self._h, None
+        if h is not None and self._token.alive and _lib is not None:
+            _lib.pbrt_gpu_buffer_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:   # interpreter teardown: module globals may already be gone
+            pass
+
+
+def check_buffers(renderer, n, bufs):
+    """The bounds protection of the device-query calls: every (name, buffer,
+    dtype) of bufs must be an open DeviceBuffer of this renderer, of that dtype
+    and of at least n elements. Raises PbrtError(PBRT_E_INVALID) before anything
+    reaches the library; needs no context."""
+    if not isinstance(n, (int, np.integer)) or n < 0 or n > 2**31 - 1:
+        raise PbrtError(abi.PBRT_E_INVALID, f"ray count {n!r} outside 0 .. 2^31 - 1")
+    for name, b, dtype in bufs:
+        if not isinstance(b, DeviceBuffer):
+            raise PbrtError(abi.PBRT_E_INVALID, f"{name}: not a DeviceBuffer")
+        if b.closed:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{name}: the buffer is closed")
+        if b.renderer is not renderer:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{name}: the buffer belongs to another Renderer")
+        if b.dtype != np.dtype(dtype):
+            raise PbrtError(abi.PBRT_E_INVALID, f"{name}: {b.dtype} buffer where {np.dtype(dtype)} is needed")
+        if b.n < n:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{name}: {b.n} elements for {n} rays")
+
+
+def _ray_bufs(rays):
+    """rays as [(name, buffer, dtype)]: a dict with ox..dz and an optional tmax,
+    or a tuple of 6 or 7 buffers in that order."""
+    if not isinstance(rays, dict):
+        rays = tuple(rays)
+        if len(rays) not in (6, 7):
+            raise PbrtError(abi.PBRT_E_INVALID, "rays: 6 buffers (ox..dz) or 7 (with tmax)")
+        rays = dict(zip(RAY_KEYS + ("tmax",), rays))
+    unknown = set(rays) - set(RAY_KEYS) - {"tmax"}
+    missing = [k for k in RAY_KEYS if rays.get(k) is None]
+    if unknown or missing:
+        raise PbrtError(abi.PBRT_E_INVALID, f"rays: unknown {sorted(unknown)}, missing {missing}")
+    return [(k, rays[k], np.float64) for k in RAY_KEYS + ("tmax",) if rays.get(k) is not None]
+
+
+def _soa(struct, bufs):
+    """A ctypes SoA struct whose fields point at the (checked) buffers."""
+    s = struct()
+    for name, b, _ in bufs:
+        setattr(s, name, C.cast(C.c_void_p(b.ptr), dict(struct._fields_)[name]))
+    return s
+
+
 # --------------------------------------------------------------------- renderer
 class Renderer:
     """pbrt_gpu_ctx: the scene resident on one GPU."""
@@ -395,6 +520,9 @@ class Renderer:
     def __init__(self, scene, device=-1, lanes_per_wave=0, occupancy=0, kernel="auto"):
         desc = scene.desc if isinstance(scene, Scene) else scene
         self._scene = scene  # keep the descriptor alive
+        self._token = ContextToken()   # shared with every DeviceBuffer of this context
+        self._primary = {}             # primary_hits: (w, h) -> its buffers
+        self.res = (int(desc.film.res_x), int(desc.film.res_y))
         opts = abi.GpuOpts()
         opts.device, opts.lanes_per_wave = device, lanes_per_wave
         opts.occupancy, opts.kernel = occupancy, self.KERNELS[kernel]
@@ -534,7 +662,94 @@ class Renderer:
         rc = lib().pbrt_gpu_intersect_p(self.h, C.byref(soa), n, occ.ctypes.data_as(C.POINTER(C.c_uint8)))
         return rc, occ
 
+    # ---- device-resident queries: numpy and ctypes only; the device memory is
+    # the context's own (DeviceBuffer), so nothing here can outlive the context
+    def buffer(self, n, dtype=np.float64):
+        """A DeviceBuffer of n elements (float64, int32 or uint8), uninitialised."""
+        dtype = np.dtype(dtype)
+        if dtype not in BUFFER_DTYPES or n <= 0:
+            raise PbrtError(abi.PBRT_E_INVALID, f"buffer of {n} x {dtype}: float64, int32 or uint8, n > 0")
+        if not getattr(self, "h", None):
+            raise PbrtError(abi.PBRT_E_INVALID, "the Renderer is closed")
+        h = C.c_void_p()
+        self._check(lib().pbrt_gpu_buffer_create(self.h, int(n) * dtype.itemsize, C.byref(h)))
+        return DeviceBuffer(self, h.value, lib().pbrt_gpu_buffer_ptr(h.value), n, dtype)
+
+    def upload(self, array):
+        """A DeviceBuffer holding a copy of a 1-D host array."""
+        a = np.ascontiguousarray(array).reshape(-1)
+        return self.buffer(a.size, a.dtype).upload(a)
+
+    def intersect_device(self, rays, n, hits):
+        """pbrt_gpu_intersect_device: closest hits of rays[0:n] into the buffers of
+        hits ({"hit": uint8, and any of t_max, prim (int32), px..nz}). Enqueue only:
+        read the results with DeviceBuffer.download() or after query_status().
+        Returns the status (PBRT_E_INVALID while a render is in flight)."""
+        unknown = set(hits) - set(HIT_DTYPES)
+        if unknown or hits.get("hit") is None:
+            raise PbrtError(abi.PBRT_E_INVALID, f"hits: 'hit' is required; unknown {sorted(unknown)}")
+        rb = _ray_bufs(rays)
+        hb = [(k, hits[k], HIT_DTYPES[k]) for k in HIT_DTYPES if hits.get(k) is not None]
+        check_buffers(self, n, rb + hb)
+        rs, hs = _soa(abi.RaySoA, rb), _soa(abi.HitSoA, hb)
+        return lib().pbrt_gpu_intersect_device(self.h, C.byref(rs), n, C.byref(hs))
+
+    def intersect_p_device(self, rays, n, occluded):
+        """pbrt_gpu_intersect_p_device: any-hit flags (uint8 buffer) of rays[0:n]."""
+        rb = _ray_bufs(rays)
+        check_buffers(self, n, rb + [("occluded", occluded, np.uint8)])
+        rs = _soa(abi.RaySoA, rb)
+        return lib().pbrt_gpu_intersect_p_device(self.h, C.byref(rs), n, C.c_void_p(occluded.ptr))
+
+    def camera_rays(self, window=None, film_offset=(0.5, 0.5), lens=(0.5, 0.5), time_u=0.0, out=None):
+        """pbrt_gpu_camera_rays_device: the camera rays of the pixel window (x0, y0,
+        x1, y1) (None: the whole film resolution) in raster order, pFilm = pixel +
+        film_offset. out: ray buffers as intersect_device takes them (tmax
+        optional); None allocates seven. Returns them as a dict."""
+        x0, y0, x1, y1 = (0, 0) + self.res if window is None else (int(v) for v in window)
+        if not (0 <= x0 < x1 <= self.res[0] and 0 <= y0 < y1 <= self.res[1]):
+            raise PbrtError(abi.PBRT_E_INVALID, f"window {(x0, y0, x1, y1)} outside the film {self.res}")
+        n = (x1 - x0) * (y1 - y0)
+        if out is None:
+            out = {k: self.buffer(n) for k in RAY_KEYS + ("tmax",)}
+        rb = _ray_bufs(out)
+        check_buffers(self, n, rb)
+        d = abi.CameraRaysDesc(x0, y0, x1, y1, film_offset[0], film_offset[1], lens[0], lens[1], time_u)
+        rs = _soa(abi.RaySoAOut, rb)
+        self._check(lib().pbrt_gpu_camera_rays_device(self.h, C.byref(d), C.byref(rs)))
+        return {k: b for k, b, _ in rb}
+
+    def query_status(self):
+        """(status, QueryRecord) of the queries since the last call: synchronises
+        the stream; PBRT_E_REF_PANIC when the reference panics on some ray."""
+        rec = abi.QueryRecord()
+        rc = lib().pbrt_gpu_query_status(self.h, C.byref(rec))
+        return rc, rec
+
+    def primary_hits(self, window=None, **offsets):
+        """Primary visibility of a pixel window: camera rays chained into a
+        closest-hit query on the context's stream, with no host step or copy.
+        Returns {"n", "rays": {...}, "hits": {...}} of DeviceBuffers, allocated
+        once per window size and reused (so valid until the next call of that
+        size); offsets are camera_rays' film_offset, lens and time_u."""
+        x0, y0, x1, y1 = (0, 0) + self.res if window is None else (int(v) for v in window)
+        n = (x1 - x0) * (y1 - y0)
+        bufs = self._primary.get((x1 - x0, y1 - y0))
+        if bufs is None or any(b.closed for part in bufs for b in part.values()):
+            if n <= 0:
+                raise PbrtError(abi.PBRT_E_INVALID, f"empty window {(x0, y0, x1, y1)}")
+            bufs = ({k: self.buffer(n) for k in RAY_KEYS + ("tmax",)},
+                    {k: self.buffer(n, dt) for k, dt in HIT_DTYPES.items()})
+            self._primary[(x1 - x0, y1 - y0)] = bufs
+        rays, hits = bufs
+        self.camera_rays((x0, y0, x1, y1), out=rays, **offsets)
+        self._check(self.intersect_device(rays, n, hits))
+        return {"n": n, "rays": dict(rays), "hits": dict(hits)}
+
     def close(self):
+        if getattr(self, "_token", None) is not None:
+            self._token.alive = False   # every DeviceBuffer of this context is closed from here on
+            self._primary = {}
         if getattr(self, "h", None):
             lib().pbrt_gpu_destroy(self.h)
             self.h = None

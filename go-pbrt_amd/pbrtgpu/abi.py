@@ -305,3 +305,50 @@ def declare_group(L):
     L.pbrt_gpu_group_last_error.restype = C.c_char_p
     L.pbrt_gpu_group_destroy.argtypes = [vp]
     L.pbrt_gpu_group_destroy.restype = None
+
+
+# ------------------------------------------------------- device-resident queries
+class RaySoAOut(C.Structure):
+    """pbrt_ray_soa_out: device arrays pbrt_gpu_camera_rays_device writes."""
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "tmax")]
+
+
+class CameraRaysDesc(C.Structure):
+    _fields_ = [
+        ("x0", C.c_int64),
+        ("y0", C.c_int64),
+        ("x1", C.c_int64),
+        ("y1", C.c_int64),
+        ("film_dx", C.c_double),
+        ("film_dy", C.c_double),
+        ("lens_u", C.c_double),
+        ("lens_v", C.c_double),
+        ("time_u", C.c_double),
+    ]
+
+
+class QueryRecord(C.Structure):
+    _fields_ = [("panics", C.c_uint64), ("first_ray", C.c_int64), ("panic_kind", C.c_int32), ("pad0", C.c_int32)]
+
+
+QUERY_SYMBOLS = ("pbrt_gpu_buffer_create", "pbrt_gpu_buffer_ptr", "pbrt_gpu_buffer_size", "pbrt_gpu_buffer_upload",
+                 "pbrt_gpu_buffer_download", "pbrt_gpu_buffer_destroy", "pbrt_gpu_intersect_device",
+                 "pbrt_gpu_intersect_p_device", "pbrt_gpu_camera_rays_device", "pbrt_gpu_query_status")
+
+
+def declare_query(L):
+    """ctypes prototypes of the buffer and device-query entry points."""
+    P, vp, sz = C.POINTER, C.c_void_p, C.c_size_t
+    L.pbrt_gpu_buffer_create.argtypes = [vp, sz, P(vp)]
+    L.pbrt_gpu_buffer_ptr.argtypes = [vp]
+    L.pbrt_gpu_buffer_ptr.restype = vp
+    L.pbrt_gpu_buffer_size.argtypes = [vp]
+    L.pbrt_gpu_buffer_size.restype = sz
+    L.pbrt_gpu_buffer_upload.argtypes = [vp, sz, vp, sz]
+    L.pbrt_gpu_buffer_download.argtypes = [vp, sz, vp, sz]
+    L.pbrt_gpu_buffer_destroy.argtypes = [vp]
+    L.pbrt_gpu_buffer_destroy.restype = None
+    L.pbrt_gpu_intersect_device.argtypes = [vp, P(RaySoA), sz, P(HitSoA)]
+    L.pbrt_gpu_intersect_p_device.argtypes = [vp, P(RaySoA), sz, vp]
+    L.pbrt_gpu_camera_rays_device.argtypes = [vp, P(CameraRaysDesc), P(RaySoAOut)]
+    L.pbrt_gpu_query_status.argtypes = [vp, P(QueryRecord)]

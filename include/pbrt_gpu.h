@@ -352,6 +352,80 @@ int pbrt_gpu_intersect(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, size_t n,
 int pbrt_gpu_intersect_p(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, size_t n,
                          uint8_t* occluded);
 
+/* ---------------------------------------------------- device-resident queries */
+/* Device memory owned by a context, for callers that cannot allocate on the
+ * device themselves (Go) or should not hand the library memory whose lifetime
+ * another runtime manages. A buffer is freed by pbrt_gpu_buffer_destroy or, at
+ * the latest, by pbrt_gpu_destroy of its context (after the context's streams
+ * have been synchronised); using a handle after its context is destroyed is
+ * undefined. bytes == 0 is PBRT_E_INVALID. upload and download are ordered on
+ * the context's stream and synchronise it: they return when the host memory
+ * may be reused (upload) or is valid (download). A range outside the buffer is
+ * PBRT_E_INVALID. buffer_destroy synchronises the stream first. */
+typedef struct pbrt_gpu_buffer pbrt_gpu_buffer;
+int pbrt_gpu_buffer_create(pbrt_gpu_ctx* ctx, size_t bytes, pbrt_gpu_buffer** out);
+void* pbrt_gpu_buffer_ptr(const pbrt_gpu_buffer* b);
+size_t pbrt_gpu_buffer_size(const pbrt_gpu_buffer* b);
+int pbrt_gpu_buffer_upload(pbrt_gpu_buffer* b, size_t offset, const void* host, size_t bytes);
+int pbrt_gpu_buffer_download(pbrt_gpu_buffer* b, size_t offset, void* host, size_t bytes);
+void pbrt_gpu_buffer_destroy(pbrt_gpu_buffer* b);
+
+/* pbrt_gpu_intersect[_p] over arrays that already live on the device: every
+ * pointer of rays and hits (and occluded) is a DEVICE pointer to n elements,
+ * from pbrt_gpu_buffer_ptr or any allocation of the context's device. The calls
+ * only enqueue a kernel on the context's stream (pbrt_gpu_stream), after
+ * everything already on it: no allocation, copy or synchronisation (but one
+ * small allocation for the panic record on a context's first query), so the
+ * outputs are valid once the stream has been synchronised (pbrt_gpu_query_status,
+ * pbrt_gpu_buffer_download, or the caller's own stream wait).
+ *
+ * rays->tmax may be NULL (+Inf). hits->hit is required, every other pointer of
+ * hits is optional. Values are those of pbrt_gpu_intersect: on a miss hit 0,
+ * t_max the ray's own TMax, prim -1, point and normal 0; occluded is 1 or 0. A
+ * ray on which the reference panics is written as a miss (occluded 0) and
+ * counted in the context's panic record. n == 0 is PBRT_OK and launches
+ * nothing. PBRT_E_INVALID, before any device call: a NULL context, rays, ray
+ * pointer other than tmax, hits->hit or occluded; n > 2^31 - 1; or a render in
+ * flight on the context (between render_async and its synchronize), which is
+ * left untouched. */
+int pbrt_gpu_intersect_device(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, size_t n,
+                              const pbrt_hit_soa* hits);
+int pbrt_gpu_intersect_p_device(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, size_t n,
+                                uint8_t* occluded);
+
+/* Camera rays of a pixel window, written to device arrays in raster order:
+ * ray (y - y0) * (x1 - x0) + (x - x0) is PerspectiveCamera.GenerateRay
+ * (camera.go:192-242) for pFilm = (x + film_dx, y + film_dy), pLens = (lens_u,
+ * lens_v) and time sample time_u, with TMax +Inf (tmax may be NULL: not
+ * written). Enqueue-only and ordered like the intersect calls, so an
+ * intersect_device on its output needs no host step in between. A window
+ * outside 0 <= x0 < x1 <= res_x (same for y) is PBRT_E_INVALID. */
+typedef struct pbrt_ray_soa_out {
+    double *ox, *oy, *oz, *dx, *dy, *dz;
+    double *tmax;                /* may be NULL                              */
+} pbrt_ray_soa_out;
+typedef struct pbrt_camera_rays_desc {
+    int64_t x0, y0, x1, y1;
+    double film_dx, film_dy;
+    double lens_u, lens_v, time_u;
+} pbrt_camera_rays_desc;
+int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* ctx, const pbrt_camera_rays_desc* desc,
+                                const pbrt_ray_soa_out* rays);
+
+/* The panic record of every query since the last pbrt_gpu_query_status:
+ * panics counts the rays on which the reference would have panicked,
+ * first_ray is the smallest index (within its call) of such a ray, -1 when
+ * there was none, and panic_kind that ray's PBRT_PANIC_*. The call synchronises
+ * the context's stream, copies the record to *out (may be NULL) and clears it;
+ * it returns PBRT_E_REF_PANIC when panics > 0, else PBRT_OK, and
+ * PBRT_E_INVALID for a NULL context or a render in flight. */
+typedef struct pbrt_query_record {
+    uint64_t panics;
+    int64_t first_ray;
+    int32_t panic_kind, pad0;
+} pbrt_query_record;
+int pbrt_gpu_query_status(pbrt_gpu_ctx* ctx, pbrt_query_record* out);
+
 /* Cancels the render in flight on ctx (from pbrt_gpu_render[_async[_into]]
  * entry until its pbrt_gpu_synchronize returns): the kernels poll a flag between
  * units of work (a pixel's chain, every 128 chain steps, a workgroup of paths),

@@ -569,3 +569,77 @@ func (b *BVH) IntersectPBatch(rays []*pbrt.Ray, occluded []bool) error {
 	}
 	return nil
 }
+
+// ------------------------------------------------- device-resident batches
+// For callers whose rays are made on the device (CameraRaysDevice) or reused
+// over several queries: the arrays live in DeviceBuffers of the BVH's
+// renderer, the calls only enqueue, and QueryStatus waits and reports.
+
+// NewDeviceBuffer allocates device memory owned by the BVH's renderer.
+func (b *BVH) NewDeviceBuffer(bytes int) (*DeviceBuffer, error) {
+	if err := b.device(); err != nil {
+		return nil, err
+	}
+	return b.renderer.NewDeviceBuffer(bytes)
+}
+
+// UploadRays copies rays into seven new float64 DeviceBuffers (ox..dz, tmax).
+func (b *BVH) UploadRays(rays []*pbrt.Ray) (DeviceRays, error) {
+	var dr DeviceRays
+	n := len(rays)
+	if n == 0 || n > maxBatchRays {
+		return dr, fmt.Errorf("pbrtgpu: %d rays in one device batch (1 .. %d)", n, maxBatchRays)
+	}
+	if err := b.device(); err != nil {
+		return dr, err
+	}
+	col := make([]float64, n) // passed to C for the call only: holds no pointers
+	dst := []**DeviceBuffer{&dr.Ox, &dr.Oy, &dr.Oz, &dr.Dx, &dr.Dy, &dr.Dz, &dr.TMax}
+	for k := range dst {
+		for i, r := range rays {
+			col[i] = [7]float64{r.Origin.X, r.Origin.Y, r.Origin.Z, r.Direction.X, r.Direction.Y, r.Direction.Z, r.TMax}[k]
+		}
+		d, err := b.renderer.NewDeviceBuffer(8 * n)
+		if err == nil {
+			err = d.Upload(0, col)
+		}
+		if err != nil {
+			return dr, err
+		}
+		*dst[k] = d
+	}
+	return dr, nil
+}
+
+// IntersectDeviceBatch is BVH.Intersect (bvh.go:659-712) for rays[0:n] on the
+// device; hits.Prim receives BVH slots (-1 on a miss; PrimitiveOfSlot maps them).
+func (b *BVH) IntersectDeviceBatch(rays DeviceRays, n int, hits DeviceHits) error {
+	if err := b.device(); err != nil {
+		return err
+	}
+	return b.renderer.IntersectDevice(rays, n, hits)
+}
+
+// IntersectPDeviceBatch is BVH.IntersectP (bvh.go:713-765) the same way.
+func (b *BVH) IntersectPDeviceBatch(rays DeviceRays, n int, occluded *DeviceBuffer) error {
+	if err := b.device(); err != nil {
+		return err
+	}
+	return b.renderer.IntersectPDevice(rays, n, occluded)
+}
+
+// QueryStatus waits for the enqueued batches and returns their panic record.
+func (b *BVH) QueryStatus() (QueryPanics, error) {
+	if err := b.device(); err != nil {
+		return QueryPanics{}, err
+	}
+	return b.renderer.QueryStatus()
+}
+
+// PrimitiveOfSlot maps a downloaded hits.Prim value to the NewBVH input primitive (nil: a miss).
+func (b *BVH) PrimitiveOfSlot(slot int32) pbrt.Primitive {
+	if slot < 0 || int(slot) >= len(b.slotPrim) {
+		return nil
+	}
+	return b.rec.order[b.slotPrim[slot]]
+}

@@ -5,7 +5,9 @@
 //   - pbrt.Render / renderWorker (pkg/pbrt/integrator.go:228-350) with
 //     Renderer.RenderFrame (Path.Li and DirectLighting.Li run on the device);
 //   - (*accelerator.BVH).Intersect / IntersectP (pkg/accelerator/bvh.go:659-765)
-//     with Renderer.Intersect / IntersectP over ray batches;
+//     with Renderer.Intersect / IntersectP over ray batches, and with
+//     IntersectDevice / IntersectPDevice / CameraRaysDevice over DeviceBuffers
+//     for rays and results that stay on the device;
 //   - Film.WriteImage's pixel conversion (pkg/pbrt/film.go:142-179) with FilmToRGBA.
 //
 // The reference's constructors (internal/render/server.go:32-164) keep their
@@ -196,6 +198,7 @@ func WithRandomSampler(rd *C.pbrt_render_desc, ns int32) { C.pbrt_random_sampler
 type Renderer struct {
 	ctx  *C.pbrt_gpu_ctx
 	w, h int // CroppedPixelBounds extent of the scene's film
+	bufs map[*DeviceBuffer]struct{} // its open device buffers (NewDeviceBuffer)
 }
 
 func NewRenderer(s *SceneBuilder, device int) (*Renderer, error) {
@@ -290,7 +293,232 @@ func (r *Renderer) IntersectP(rays *C.pbrt_ray_soa, n int, occluded []uint8) err
 	return nil
 }
 
-func (r *Renderer) Close() { C.pbrt_gpu_destroy(r.ctx) }
+// Close destroys the context. Its device buffers go with it (pbrt_gpu_destroy
+// frees what is left), so every DeviceBuffer still open is marked closed first
+// and can no longer reach the library.
+func (r *Renderer) Close() {
+	for d := range r.bufs {
+		d.b = nil
+	}
+	r.bufs = nil
+	C.pbrt_gpu_destroy(r.ctx)
+}
+
+// ---------------------------------------------------- device-resident queries
+
+// DeviceBuffer is pbrt_gpu_buffer: device memory the Renderer's context owns.
+// Go cannot allocate on the device, so rays and results that stay there live
+// in these. A buffer is closed by Close or by its Renderer's Close, whichever
+// comes first; a closed buffer fails every call.
+type DeviceBuffer struct {
+	r *Renderer
+	b *C.pbrt_gpu_buffer
+}
+
+func (r *Renderer) NewDeviceBuffer(bytes int) (*DeviceBuffer, error) {
+	if bytes <= 0 {
+		return nil, fmt.Errorf("pbrtgpu: device buffer of %d bytes", bytes)
+	}
+	var b *C.pbrt_gpu_buffer
+	if rc := C.pbrt_gpu_buffer_create(r.ctx, C.size_t(bytes), &b); rc != C.PBRT_OK {
+		return nil, fmt.Errorf("pbrt_gpu_buffer_create: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	d := &DeviceBuffer{r: r, b: b}
+	if r.bufs == nil {
+		r.bufs = map[*DeviceBuffer]struct{}{}
+	}
+	r.bufs[d] = struct{}{}
+	return d, nil
+}
+
+// Size is the buffer's size in bytes (0 once closed).
+func (d *DeviceBuffer) Size() int { return int(C.pbrt_gpu_buffer_size(d.b)) }
+
+func (d *DeviceBuffer) copy(offset int, host unsafe.Pointer, bytes int, up bool) error {
+	if d.b == nil {
+		return fmt.Errorf("pbrtgpu: device buffer is closed")
+	}
+	if offset < 0 || bytes < 0 || offset+bytes > d.Size() {
+		return fmt.Errorf("pbrtgpu: bytes [%d, %d) outside a buffer of %d", offset, offset+bytes, d.Size())
+	}
+	rc := C.int(C.PBRT_OK)
+	if up {
+		rc = C.pbrt_gpu_buffer_upload(d.b, C.size_t(offset), host, C.size_t(bytes))
+	} else {
+		rc = C.pbrt_gpu_buffer_download(d.b, C.size_t(offset), host, C.size_t(bytes))
+	}
+	if rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_buffer copy: %s", C.GoString(C.pbrt_gpu_last_error(d.r.ctx)))
+	}
+	return nil
+}
+
+// Upload copies src to the buffer at byte offset; it returns once src may be reused.
+func (d *DeviceBuffer) Upload(offset int, src []float64) error {
+	if len(src) == 0 {
+		return nil
+	}
+	return d.copy(offset, unsafe.Pointer(&src[0]), 8*len(src), true)
+}
+
+// UploadBytes, DownloadBytes: the same for uint8 (hit flags) or raw int32 data.
+func (d *DeviceBuffer) UploadBytes(offset int, src []byte) error {
+	if len(src) == 0 {
+		return nil
+	}
+	return d.copy(offset, unsafe.Pointer(&src[0]), len(src), true)
+}
+
+// Download fills dst from the buffer at byte offset (synchronises the context's stream).
+func (d *DeviceBuffer) Download(offset int, dst []float64) error {
+	if len(dst) == 0 {
+		return nil
+	}
+	return d.copy(offset, unsafe.Pointer(&dst[0]), 8*len(dst), false)
+}
+
+func (d *DeviceBuffer) DownloadBytes(offset int, dst []byte) error {
+	if len(dst) == 0 {
+		return nil
+	}
+	return d.copy(offset, unsafe.Pointer(&dst[0]), len(dst), false)
+}
+
+func (d *DeviceBuffer) Close() {
+	if d.b == nil {
+		return
+	}
+	delete(d.r.bufs, d)
+	C.pbrt_gpu_buffer_destroy(d.b)
+	d.b = nil
+}
+
+// DeviceRays are the ray arrays of a device query (float64 each); TMax may be
+// nil (+Inf on input, not written by CameraRaysDevice).
+type DeviceRays struct{ Ox, Oy, Oz, Dx, Dy, Dz, TMax *DeviceBuffer }
+
+// DeviceHits are the outputs of IntersectDevice: Hit (uint8) is required, TMax,
+// Point, Normal (float64) and Prim (int32) may be nil.
+type DeviceHits struct{ Hit, TMax, Prim, Px, Py, Pz, Nx, Ny, Nz *DeviceBuffer }
+
+// devPtr is the only bounds protection a device query gets: the buffer must be
+// open, belong to this Renderer and hold n elements of elem bytes.
+func (r *Renderer) devPtr(d *DeviceBuffer, n, elem int, optional bool) (unsafe.Pointer, error) {
+	if d == nil {
+		if optional {
+			return nil, nil
+		}
+		return nil, fmt.Errorf("pbrtgpu: a required device buffer is nil")
+	}
+	if d.b == nil || d.r != r {
+		return nil, fmt.Errorf("pbrtgpu: device buffer closed or of another Renderer")
+	}
+	if n < 0 || n > 1<<31-1 || n*elem > d.Size() {
+		return nil, fmt.Errorf("pbrtgpu: %d elements of %d bytes in a buffer of %d", n, elem, d.Size())
+	}
+	return C.pbrt_gpu_buffer_ptr(d.b), nil
+}
+
+func (r *Renderer) raySoA(rays DeviceRays, n int) (C.pbrt_ray_soa, error) {
+	var soa C.pbrt_ray_soa
+	p := [7]unsafe.Pointer{}
+	for k, d := range []*DeviceBuffer{rays.Ox, rays.Oy, rays.Oz, rays.Dx, rays.Dy, rays.Dz, rays.TMax} {
+		q, err := r.devPtr(d, n, 8, k == 6)
+		if err != nil {
+			return soa, err
+		}
+		p[k] = q
+	}
+	soa.ox, soa.oy, soa.oz = (*C.double)(p[0]), (*C.double)(p[1]), (*C.double)(p[2])
+	soa.dx, soa.dy, soa.dz = (*C.double)(p[3]), (*C.double)(p[4]), (*C.double)(p[5])
+	soa.tmax = (*C.double)(p[6])
+	return soa, nil
+}
+
+// IntersectDevice enqueues BVH.Intersect for rays[0:n] on the context's stream
+// (pbrt_gpu_intersect_device): nothing is copied or waited for. Results are
+// valid after QueryStatus or a Download.
+func (r *Renderer) IntersectDevice(rays DeviceRays, n int, hits DeviceHits) error {
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return err
+	}
+	var hs C.pbrt_hit_soa
+	p := [9]unsafe.Pointer{}
+	elem := [9]int{1, 8, 4, 8, 8, 8, 8, 8, 8}
+	for k, d := range []*DeviceBuffer{hits.Hit, hits.TMax, hits.Prim, hits.Px, hits.Py, hits.Pz, hits.Nx, hits.Ny, hits.Nz} {
+		if p[k], err = r.devPtr(d, n, elem[k], k > 0); err != nil {
+			return err
+		}
+	}
+	hs.hit, hs.t_max, hs.prim = (*C.uint8_t)(p[0]), (*C.double)(p[1]), (*C.int32_t)(p[2])
+	hs.px, hs.py, hs.pz = (*C.double)(p[3]), (*C.double)(p[4]), (*C.double)(p[5])
+	hs.nx, hs.ny, hs.nz = (*C.double)(p[6]), (*C.double)(p[7]), (*C.double)(p[8])
+	if rc := C.pbrt_gpu_intersect_device(r.ctx, &soa, C.size_t(n), &hs); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_intersect_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// IntersectPDevice is BVH.IntersectP the same way; occluded holds n uint8.
+func (r *Renderer) IntersectPDevice(rays DeviceRays, n int, occluded *DeviceBuffer) error {
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return err
+	}
+	occ, err := r.devPtr(occluded, n, 1, false)
+	if err != nil {
+		return err
+	}
+	if rc := C.pbrt_gpu_intersect_p_device(r.ctx, &soa, C.size_t(n), (*C.uint8_t)(occ)); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_intersect_p_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// CameraRaysDevice writes the camera rays of the pixel window [x0, x1) x [y0, y1)
+// in raster order (pbrt_gpu_camera_rays_device), pFilm = pixel + filmOffset; an
+// IntersectDevice on them needs no host step in between.
+func (r *Renderer) CameraRaysDevice(x0, y0, x1, y1 int64, filmOffset, lens [2]float64, timeU float64, rays DeviceRays) error {
+	if x0 < 0 || y0 < 0 || x0 >= x1 || y0 >= y1 {
+		return fmt.Errorf("pbrtgpu: empty pixel window")
+	}
+	soa, err := r.raySoA(rays, int((x1-x0)*(y1-y0)))
+	if err != nil {
+		return err
+	}
+	var out C.pbrt_ray_soa_out
+	out.ox, out.oy, out.oz, out.dx, out.dy, out.dz, out.tmax = soa.ox, soa.oy, soa.oz, soa.dx, soa.dy, soa.dz, soa.tmax
+	var cd C.pbrt_camera_rays_desc
+	cd.x0, cd.y0, cd.x1, cd.y1 = C.int64_t(x0), C.int64_t(y0), C.int64_t(x1), C.int64_t(y1)
+	cd.film_dx, cd.film_dy = C.double(filmOffset[0]), C.double(filmOffset[1])
+	cd.lens_u, cd.lens_v, cd.time_u = C.double(lens[0]), C.double(lens[1]), C.double(timeU)
+	if rc := C.pbrt_gpu_camera_rays_device(r.ctx, &cd, &out); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_camera_rays_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// QueryPanics is pbrt_query_record: how many rays of the queries since the last
+// QueryStatus the reference panics on, the smallest such ray index (-1: none)
+// and its PBRT_PANIC_* kind.
+type QueryPanics struct {
+	Panics   uint64
+	FirstRay int64
+	Kind     int32
+}
+
+// QueryStatus waits for the context's stream and returns (and clears) the panic
+// record. Unlike RenderFrame it does not panic: a batch reports, the caller decides.
+func (r *Renderer) QueryStatus() (QueryPanics, error) {
+	var rec C.pbrt_query_record
+	rc := C.pbrt_gpu_query_status(r.ctx, &rec)
+	qp := QueryPanics{Panics: uint64(rec.panics), FirstRay: int64(rec.first_ray), Kind: int32(rec.panic_kind)}
+	if rc != C.PBRT_OK && rc != C.PBRT_E_REF_PANIC {
+		return qp, fmt.Errorf("pbrt_gpu_query_status: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return qp, nil
+}
 
 // RendererGroup owns the scene resident on several GPUs (pbrt_gpu_group): the
 // frame's tiles are split over the devices and merged on the first of them in
