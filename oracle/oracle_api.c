@@ -173,6 +173,25 @@ int oracle_triangle_hit(const double v[9], const double ray[7], double out[4]) {
     r.time = 0;
     return orc_triangle_hit(v, &r, &out[0], &out[1], &out[2], &out[3]);
 }
+/* (input triangles, triangles kept in the oracle's tree) of the scene's meshes */
+void oracle_mesh_counts(const pbrt_scene_desc* sc, int64_t out[2]) { orc_mesh_counts(orc_mesh_get(sc), out); }
+/* the same test of one ray against n triangles (brute force, no accelerator):
+ * hit[i] and, where hit, t[i]; returns the number of hits */
+int64_t oracle_triangle_hits(const double* v, int64_t n, const double ray[7], uint8_t* hit, double* t) {
+    ray_t r;
+    r.o = V3(ray[0], ray[1], ray[2]);
+    r.d = V3(ray[3], ray[4], ray[5]);
+    r.tmax = ray[6];
+    r.time = 0;
+    int64_t count = 0;
+    for (int64_t i = 0; i < n; i++) {
+        double b0, b1, b2;
+        t[i] = 0;
+        hit[i] = (uint8_t)orc_triangle_hit(v + 9 * i, &r, &t[i], &b0, &b1, &b2);
+        count += hit[i];
+    }
+    return count;
+}
 
 /* ---------------------------------- pkg/geometry/xyz_test.go, spectrum_test.go */
 #include "../include/pbrt_diag.h"

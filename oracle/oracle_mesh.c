@@ -158,6 +158,9 @@ static pthread_mutex_t g_lock = PTHREAD_MUTEX_INITIALIZER;
 static orc_mesh* g_mesh;
 static uint64_t g_key;
 
+/* The cache key covers everything the tree and the hits depend on: every
+ * vertex bit and every index of every mesh (one pass; a sampled key let a
+ * scene of equal sizes at a reused address pick up the previous scene's tree). */
 static uint64_t mesh_key(const pbrt_scene_desc* sc) {
     uint64_t h = 1469598103934665603ull;
 #define MIX(x) (h = (h ^ (uint64_t)(x)) * 1099511628211ull)
@@ -166,11 +169,12 @@ static uint64_t mesh_key(const pbrt_scene_desc* sc) {
         const pbrt_mesh_desc* d = &sc->meshes[mi];
         MIX(d->n_vertices); MIX(d->n_triangles); MIX(d->material); MIX(d->reverse_orientation);
         MIX((uintptr_t)d->p); MIX((uintptr_t)d->indices);
-        for (int32_t i = 0; i < 3 * d->n_vertices; i += 1 + 3 * d->n_vertices / 64) {
+        for (int64_t i = 0; i < 3 * (int64_t)d->n_vertices; i++) {
             uint32_t b;
             memcpy(&b, &d->p[i], 4);
             MIX(b);
         }
+        for (int64_t i = 0; i < 3 * (int64_t)d->n_triangles; i++) MIX((uint32_t)d->indices[i]);
     }
 #undef MIX
     return h;
@@ -220,6 +224,11 @@ const orc_mesh* orc_mesh_get(const pbrt_scene_desc* sc) {
     g_key = key;
     pthread_mutex_unlock(&g_lock);
     return m;
+}
+
+void orc_mesh_counts(const orc_mesh* m, int64_t out[2]) {
+    out[0] = m ? m->n_tris : 0;
+    out[1] = m ? m->n_perm : 0;
 }
 
 /* slab test against a box rounded out in float32, inclusive of tmax */

@@ -40,6 +40,9 @@ int orc_mesh_closest(const orc_mesh* m, const ray_t* r, double tmax, int32_t bes
 /* Any triangle with 0 < t < r->tmax. */
 int orc_mesh_any(const orc_mesh* m, const ray_t* r);
 
+/* (input triangles, triangles in the tree: the input less the zero-area ones) */
+void orc_mesh_counts(const orc_mesh* m, int64_t out[2]);
+
 /* the triangle test alone (for tests): 1 = hit, t and barycentrics out */
 int orc_triangle_hit(const double v[9], const ray_t* r, double* t, double* b0, double* b1, double* b2);
 

@@ -116,6 +116,10 @@ def _bind(L):
         L.oracle_light_distribution.argtypes = [P(abi.SceneDesc), P(abi.RenderDesc), P(abi.DistributionDesc)]
         L.oracle_spawn_ray_to.argtypes = [P(d), P(d)]
         L.oracle_triangle_hit.argtypes = [P(d), P(d), P(d)]
+        L.oracle_triangle_hits.argtypes = [P(d), C.c_int64, P(d), P(C.c_uint8), P(d)]
+        L.oracle_triangle_hits.restype = C.c_int64
+        L.oracle_mesh_counts.argtypes = [P(abi.SceneDesc), P(C.c_int64)]
+        L.oracle_mesh_counts.restype = None
         L.oracle_vec_op.argtypes = [C.c_int, P(d), P(d), d, P(d)]
         L.oracle_partition_at.argtypes = [P(C.c_int32), P(d), C.c_int64, C.c_int64, C.c_int64, C.c_int64]
         L.oracle_partition_at.restype = C.c_int64
@@ -204,3 +208,21 @@ def triangle_hit(v, ray):
     out = np.zeros(4)
     h = lib().oracle_triangle_hit(dptr(v), dptr(ray), dptr(out))
     return bool(h), out[0], out[1], out[2], out[3]
+
+
+def mesh_counts(desc):
+    """(input triangles, triangles in the oracle's tree) of the scene's meshes."""
+    out = (C.c_int64 * 2)()
+    lib().oracle_mesh_counts(C.byref(desc), out)
+    return int(out[0]), int(out[1])
+
+
+def triangle_hits(tris, ray):
+    """orc_triangle_hit of one ray against every row of tris (n, 9), with no
+    accelerator: (hit bool [n], t [n], valid where hit)."""
+    tris = np.ascontiguousarray(tris, dtype=np.float64)
+    ray = np.ascontiguousarray(ray, dtype=np.float64)
+    n = tris.shape[0]
+    hit, t = np.zeros(n, dtype=np.uint8), np.zeros(n)
+    lib().oracle_triangle_hits(dptr(tris), n, dptr(ray), hit.ctypes.data_as(C.POINTER(C.c_uint8)), dptr(t))
+    return hit.astype(bool), t

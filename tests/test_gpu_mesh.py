@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import mesh_zoo as Z
 import oracle_lib as O
 import pbrtgpu as G
 from pbrtgpu import abi
@@ -34,7 +35,7 @@ def mesh_tris(scene):
     return p[idx].reshape(-1, 9)
 
 
-def check_wide_tree(nodes, tris, nt, info):
+def check_wide_tree(nodes, gid, tris, info, tris_in):
     """The 4-ary layout (pbrt_mesh.h MeshNode4): one tree; every node but the
     root is the child of exactly one node and names it as parent; slots
     0..count-1 hold a node or a triangle, the rest are empty; child boxes
@@ -42,7 +43,7 @@ def check_wide_tree(nodes, tris, nt, info):
     centre order along the node's axis; every triangle is one slot; the depth
     is the builder's level count and at most 32."""
     EMPTY, TRI = 0xFFFFFFFF, 0x80000000
-    n = len(nodes)
+    n, nt = len(nodes), len(gid)
     assert n >= 1 and nodes[0]["parent"] == EMPTY
     seen = np.zeros(n, dtype=np.int32)
     covered = np.zeros(nt, dtype=np.int32)
@@ -77,25 +78,12 @@ def check_wide_tree(nodes, tris, nt, info):
     assert levels == info["depth"] <= 32
 
 
-@pytest.mark.parametrize("quads", [1, 2, 3, 16, 100])
-def test_lbvh_structure(quads):
+def check_threaded_tree(nodes, gid, tris, info, tris_in):
     """Every ordering is a depth-first threading of one binary tree: leaves
     escape to the next node, the second child of an interior node starts at its
     first child's escape and ends at the node's; leaves partition the triangle
-    slots; boxes nest and contain their triangles; gid is a permutation."""
-    scene = G.Scene.heightfield(16, 16, quads=quads, seed=5)
-    tris_in = mesh_tris(scene)
-    with G.Renderer(scene) as r:
-        info = r.mesh_info()
-        nodes, gid, tris = r.mesh_download()
-    nt = 2 * quads * quads
-    assert info["tris"] == nt and info["meshes"] == 1
-    assert sorted(gid.tolist()) == list(range(nt))
-    assert np.array_equal(tris, tris_in[gid])
-    n = info["nodes"]
-    if info["wide"]:
-        check_wide_tree(nodes, tris, nt, info)
-        return
+    slots; boxes nest and contain their triangles."""
+    n, nt = info["nodes"], len(gid)
     assert nodes.shape == (8, n) and n >= 1
     recs = None
     for o in range(8):
@@ -124,6 +112,34 @@ def test_lbvh_structure(quads):
         rec = sorted((tuple(N[i]["bmin"]), tuple(N[i]["bmax"]), int(N[i]["leaf"])) for i in range(n))
         recs = rec if recs is None else recs
         assert rec == recs   # the eight orderings hold the same nodes
+
+
+def check_lbvh(nodes, gid, tris, info, tris_in):
+    """The device tree over the input triangles tris_in (global index order):
+    gid is a permutation of the kept (non-zero-area) global indices, the leaf
+    slots hold those triangles, and the tree passes its layout's checks."""
+    kept = np.flatnonzero(Z.kept_mask(tris_in))
+    assert info["tris"] == len(kept) == len(gid)
+    assert sorted(gid.tolist()) == kept.tolist()
+    assert np.array_equal(tris, tris_in[gid])
+    (check_wide_tree if info["wide"] else check_threaded_tree)(nodes, gid, tris, info, tris_in)
+
+
+@pytest.mark.parametrize("quads", [1, 2, 3, 16, 100])
+def test_lbvh_structure(quads):
+    """Every ordering is a depth-first threading of one binary tree: leaves
+    escape to the next node, the second child of an interior node starts at its
+    first child's escape and ends at the node's; leaves partition the triangle
+    slots; boxes nest and contain their triangles; gid is a permutation."""
+    scene = G.Scene.heightfield(16, 16, quads=quads, seed=5)
+    tris_in = mesh_tris(scene)
+    with G.Renderer(scene) as r:
+        info = r.mesh_info()
+        nodes, gid, tris = r.mesh_download()
+    nt = 2 * quads * quads
+    assert info["tris"] == nt and info["meshes"] == 1
+    assert Z.kept_mask(tris_in).all()   # a height field drops nothing: gid is a permutation of range(nt)
+    check_lbvh(nodes, gid, tris, info, tris_in)
 
 
 def random_rays(n, seed):

@@ -43,14 +43,24 @@ def test_triangle_edges_are_watertight():
 
 def brute_closest(tris, rays):
     """Smallest (t, index) over all triangles with t < tmax."""
+    return [(t, g) for t, g, _ in brute_ties(tris, rays)]
+
+
+def brute_ties(tris, rays):
+    """brute_closest's (t, index) and the number of triangles hit at the
+    winning t, per ray; (tmax, -1, 0) where nothing is hit below tmax. Every
+    triangle is tested (O.triangle_hits: the same orc_triangle_hit, one call
+    per ray), in index order, so the first at the smallest t wins."""
     out = []
     for r in rays:
-        best = (r[6], -1)
-        for g in range(tris.shape[0]):
-            h, t, *_ = O.triangle_hit(tris[g], r)
-            if h and (t < best[0] or (t == best[0] and best[1] >= 0 and g < best[1])):
-                best = (t, g)
-        out.append(best)
+        hit, t = O.triangle_hits(tris, r)
+        ok = hit & (t < r[6])
+        if not ok.any():
+            out.append((r[6], -1, 0))
+            continue
+        tmin = t[ok].min()
+        at = np.flatnonzero(ok & (t == tmin))
+        out.append((tmin, int(at[0]), int(at.size)))
     return out
 
 
