@@ -25,7 +25,41 @@ __device__ __forceinline__ uint32_t ring_d(const Cursor& c, const SpecSampler& s
     return kRrFlag | (d == kBadSpecD ? kRrTailBad : d);
 }
 
-template <int kW, int kDepth, bool kX, int kEu, bool kSpWin>
+// A value every lane of the wave holds alike, moved to scalar registers. The
+// compiler cannot prove an LDS load or tid / kWave wave-uniform and would keep
+// the value in a VGPR per lane for as long as it lives.
+__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ uint32_t uni(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ float uni(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ uint64_t uni(uint64_t v) {
+    return (uint64_t)uni((uint32_t)(v >> 32)) << 32 | uni((uint32_t)v);
+}
+__device__ __forceinline__ int64_t uni(int64_t v) { return (int64_t)uni((uint64_t)v); }
+// A tile's CiGroup read by every lane of its workgroup (one tile per wave or
+// per workgroup only: with several tiles per wave the lanes hold different groups)
+__device__ __forceinline__ CiGroup uni(const CiGroup& s) {
+    CiGroup u;
+    u.S = uni(s.S);
+    u.pi = uni(s.pi);
+    u.npx = uni(s.npx);
+    u.A = uni(s.A);
+    u.head = uni(s.head);
+    u.nxt = uni(s.nxt);
+    u.kh = uni(s.kh);
+    u.phase = uni(s.phase);
+    u.reissue = uni(s.reissue);
+    u.rb0 = uni(s.rb0);
+    u.rb1 = uni(s.rb1);
+    u.nb = uni(s.nb);
+    u.nnx = uni(s.nnx);
+    u.nps = uni(s.nps);
+    u.dcnt = uni(s.dcnt);
+    u.dsum = uni(s.dsum);
+    u.dsq = uni(s.dsq);
+    return u;
+}
+
+template <int kW, int kDepth, bool kX, int kEu, bool kSpWin, bool kMulti>
 // kDepth < 0 (kCiMeshOnly): scenes of triangle meshes only, no analytic walk
 // compiled in (149 VGPRs), built for 3 waves per SIMD; Matte analytic scenes
 // at PBRT_CI_EU_WAVES (3: 168 VGPRs, a few spills, faster than 2), kX at
@@ -34,6 +68,12 @@ template <int kW, int kDepth, bool kX, int kEu, bool kSpWin>
 // allows fewer than 3 waves/SIMD anyway: then the 3-wave build only spills).
 // kSpWin: the windowed wave StartPixel compiled in (rp.sp_window renders: large
 // spp without jitter, config C).
+// kMulti: several tiles per wave (opts.lanes_per_wave = 2 or 4; kW == 1): a
+// lane's group, its mask and its group's state are per-lane values. Without it
+// the workgroup has one tile, lanes_per_tile is kT, and everything derived
+// from the group (the tile's slot and PCG32 stream, the pixel record, the
+// per-step copy of the group's state) is wave-uniform and kept in scalar
+// registers: in VGPRs it cost the one-wave Matte kernel 84 B/lane of scratch.
 __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu > 0 ? kEu : kDepth < 0 ? PBRT_CI_MESH_EU_WAVES : kX ? PBRT_CI_X_EU_WAVES : PBRT_CI_EU_WAVES, 8))) void k_chain_ci(
     DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base,
     int64_t nslots_batch, int lanes_per_tile, int ring_size, Counters* __restrict__ ctr,
@@ -59,10 +99,11 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
 #ifdef PBRT_CI_DIAG
     __shared__ uint32_t dh[64];   // on-chain D histogram of the block (diagnostics)
 #endif
-    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = tid / kWave;
+    static_assert(!kMulti || kW == 1, "several tiles per wave: one-wave workgroups only");
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = kW > 1 ? uni(tid / kWave) : 0;
     stage_nodes(sc);
-    const int L = kW > 1 ? kT : lanes_per_tile, G = kW > 1 ? 1 : kWave / L;
-    const int g = kW > 1 ? 0 : lane / L, gl = kW > 1 ? tid : lane - g * L;
+    const int L = kMulti ? lanes_per_tile : kT, G = kMulti ? kWave / L : 1;
+    const int g = kMulti ? lane / L : 0, gl = kMulti ? lane - g * L : tid;
     // workgroup -> tile slot: heaviest-first order from the previous frame
     // (one tile per workgroup only), else the identity
     const int64_t blk = order ? (int64_t)order[blockIdx.x] : (int64_t)blockIdx.x;
@@ -121,8 +162,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     // tile's largest D so far (+25%) measured the same (profiles/r05/tailcap/)
     const uint32_t dmax = (uint32_t)(camera_draws(ndims) + 8 * (rp.max_depth + 1) + 8);
     const pbrt_camera_desc& cam = *sc.camera;
-    const unsigned long long gmask = L >= 64 ? ~0ULL : (((1ULL << (L & 63)) - 1ULL) << (g * L));
-    const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
+    const unsigned long long gmask = !kMulti || L >= 64 ? ~0ULL : (((1ULL << (L & 63)) - 1ULL) << (g * L));
     const int64_t bs = blk * G + g;
     const uint64_t inc = pcg_inc_of((uint64_t)tile_of_slot(rp, slot_base + (bs < nslots_batch ? bs : 0)));
 #ifdef PBRT_CI_DIAG   // diagnostics build (make diag): steps, lane-0 phase clocks, on-chain D histogram
@@ -173,7 +213,10 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     uint64_t last_host_poll = t_begin;   // when this workgroup last read the host flag
     // lane trajectory state
     uint32_t off = kNoOff;
-    int opi = -1;   // the pixel the lane's candidate belongs to
+    // the pixel the lane's candidate belongs to: the group's current pixel, or
+    // (kNps) the next. Without kNps a pixel's end drops every candidate (5), so
+    // a live candidate is always of the current pixel and the lane keeps none
+    int opi_r = -1;
     // kX: the trajectory's throughput, etaScale and start state live in LDS
     // (the BSDFX bounce needs their registers; 0 B of scratch)
 #ifdef PBRT_CI_LDS_STATE   // experiment: the Matte chain too
@@ -181,13 +224,21 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
 #else
     constexpr bool kLdsState = kX;
 #endif
+    // (the Matte throughput alone in LDS, 1536 B per wave: scratch 32 -> 20 B/lane,
+    // but config B 350 -> 402 ms, DESIGN §7: measured and not kept)
     __shared__ Spec xs_beta[kLdsState ? kT : 1];
     __shared__ double xs_eta[kLdsState ? kT : 1];
-    __shared__ uint64_t xs_st0[kLdsState ? kT : 1];
+    // One tile per workgroup: a trajectory's start state goes to its ring entry
+    // when its offset is issued, not when its draw count is known (the entry is
+    // the lane's from then on: offsets in flight lie within [head, head + R), and
+    // the walk reads it only under the tag the lane sets last), so the lane does
+    // not carry it through the trajectory
+    constexpr bool kStIssue = !kMulti;
+    __shared__ uint64_t xs_st0[kLdsState && !kStIssue ? kT : 1];
     uint64_t st0_r = 0;
     Spec beta_r = spec(1);
     double eta_r = 1.0;
-    uint64_t& st0 = [&]() -> uint64_t& { if constexpr (kLdsState) return xs_st0[tid]; else return st0_r; }();
+    uint64_t& st0 = [&]() -> uint64_t& { if constexpr (kLdsState && !kStIssue) return xs_st0[tid]; else return st0_r; }();
     Spec& beta = [&]() -> Spec& { if constexpr (kLdsState) return xs_beta[tid]; else return beta_r; }();
     double& eta_scale = [&]() -> double& { if constexpr (kLdsState) return xs_eta[tid]; else return eta_r; }();
     st0 = 0;
@@ -296,7 +347,9 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         CI_DIAG(steps++;)
 
         // ---- (2) idle lanes take the next offsets of their group
-        const CiGroup sg = gs[g];
+        CiGroup sg;
+        if constexpr (kMulti) sg = gs[g];
+        else sg = uni(gs[0]);
         const int64_t rec = bs * wb.ppt + sg.pi;
         const SpecSampler ss{wb.s1d + rec * wb.s1d_stride, n, ndims,
                              kX && wb.rrb ? wb.rrb + bs * kCiMaxRing : nullptr};
@@ -304,7 +357,9 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
             const bool idle = sg.phase == 1 && off == kNoOff;
             const unsigned long long m = __ballot(idle) & gmask;
             int nidle = __popcll(m);
-            int rank = __popcll(m & lt_mask);
+            int rank;
+            if constexpr (kMulti) rank = __popcll(m & ((1ULL << lane) - 1ULL));
+            else rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             if (kW > 1) {   // rank the idle lanes across the tile's waves
                 if (lane == 0) wcnt[wv] = nidle;
                 __syncthreads();
@@ -369,9 +424,16 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
             }
             if (o != kNoOff) {
                 off = o;
-                opi = opix;
-                st0 = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
-                c.rng.state = st0;
+                if (kNps) opi_r = opix;
+                RingEnt& e = ring_of(opix)[(off - (rpar(opix) ? sg.rb1 : sg.rb0)) & (R - 1u)];
+                if constexpr (kStIssue) {
+                    const uint64_t st = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
+                    e.st = st;
+                    c.rng.state = st;
+                } else {
+                    st0 = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
+                    c.rng.state = st0;
+                }
                 c.draws = 0;
                 c_camera(c, ndims);   // camera: Get2D pFilm, Get2D pLens, Get1D time
                 c.k = exact ? sg.kh : -1;
@@ -383,19 +445,19 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 beta = spec(1);
                 eta_scale = 1.0;
                 bounces = 1;
-                const ChainCache& pc = pcs[2 * g + rpar(opi)];
+                const ChainCache& pc = pcs[2 * g + rpar(opix)];
                 const int r = traj_scatter<kX>(sc, pc.si, pc.b, pc.x, pc.wo, c, ss, beta, eta_scale, bounces, ray,
                                                rp.max_depth, rp.rr_threshold);
                 tracing = r == 0;
                 if (r != 0) {
-                    RingEnt& e = ring_of(opi)[(off - (rpar(opi) ? sg.rb1 : sg.rb0)) & (R - 1u)];
-                    e.st = st0;
+                    if constexpr (!kStIssue) e.st = st0;
                     e.d = ring_d<kX>(c, ss, r == 1 ? c.draws : (c.k >= 0 ? kBadExactD : kBadSpecD));
                     e.tag = off;
                     off = kNoOff;
                 }
             }
         }
+        const int64_t opi = kNps ? (int64_t)opi_r : sg.pi;
         mark(1);
         CI_DIAG(const unsigned long long tbusy = __ballot(tracing); if (lane == 0) busy += (unsigned long long)__popcll(tbusy);)
         // ---- (3) one bounce of every live trajectory
@@ -434,7 +496,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
             }
             if (d != kNoOff) {
                 RingEnt& e = ring_of(opi)[(off - (rpar(opi) ? sg.rb1 : sg.rb0)) & (R - 1u)];
-                e.st = st0;
+                if constexpr (!kStIssue) e.st = st0;
                 e.d = ring_d<kX>(c, ss, d);
                 e.tag = off;
                 off = kNoOff;
@@ -445,6 +507,8 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         __syncthreads();
         // ---- (4) each group leader walks its chain through the ring
         if (gl == 0 && sg.phase == 1) {
+            // (per lane: the walk's state depends on the ring entries it loads, and
+            // reading the copy through scalar registers saved no VGPR in any build)
             CiGroup s = gs[g];
             if ((++cancel_poll & 127u) == 0) {   // long pixels (large spp)
                 const uint64_t now = wall_clock64();
@@ -558,7 +622,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         if (kNps && tid == 0 && !(gl == 0 && sg.phase == 1)) sh_act = 0;
         __syncthreads();
         if (kNps && sh_act) {   // the next pixel's ring (its parity's: the pixel before this one's) and ChainCache
-            const CiGroup s3 = gs[g];
+            const CiGroup s3 = uni(gs[0]);   // (kNps: one tile per workgroup)
             RingEnt* rn = ring_of(s3.pi + 1);
             for (uint32_t i = (uint32_t)tid; i < R; i += kT) rn[i].tag = kNoOff;
             if (tid == 0) {
@@ -574,7 +638,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         if (off != kNoOff) {
             const CiGroup s2 = gs[g];
             bool keep = false;
-            if (opi == s2.pi && s2.phase == 1)   // the current pixel
+            if ((!kNps || opi == s2.pi) && s2.phase == 1)   // the current pixel
                 keep = !(off < s2.head || (cs == 2u && ((off ^ s2.head) & 1u)) ||
                          (PBRT_CI_TAILCAP && off > s2.head + (uint32_t)(n - 1 - s2.kh) * dmax));
             else if (kNps && opi == s2.pi && s2.phase == 0)   // speculated for the pixel whose StartPixel is next

@@ -776,10 +776,13 @@ int ci_waves(const pbrt_gpu_ctx* c, int64_t nb) {
 bool ci_split_enabled(const pbrt_gpu_ctx* c) { return c->knobs.ci_split; }
 // Does a one-wave Matte k_chain_ci workgroup with `dyn_lds` bytes of dynamic
 // LDS leave room for 3 waves per SIMD (12 workgroups on a CU's LDS)?
-bool ci_eu3_fits(const pbrt_gpu_ctx* c, unsigned dyn_lds, bool lds_nodes) {
+// (`multi`: the several-tiles-per-wave instantiation, whose static LDS differs)
+bool ci_eu3_fits(const pbrt_gpu_ctx* c, unsigned dyn_lds, bool lds_nodes, bool multi = false) {
     hipFuncAttributes fa;
-    const void* f = lds_nodes ? reinterpret_cast<const void*>(&k_chain_ci<1>)
-                              : reinterpret_cast<const void*>(&k_chain_ci<1, 64>);
+    const void* f = multi ? (lds_nodes ? reinterpret_cast<const void*>(&k_chain_ci<1, 0, false, 0, false, true>)
+                                       : reinterpret_cast<const void*>(&k_chain_ci<1, 64, false, 0, false, true>))
+                    : lds_nodes ? reinterpret_cast<const void*>(&k_chain_ci<1>)
+                                : reinterpret_cast<const void*>(&k_chain_ci<1, 64>);
     size_t stat = 0;
     if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat = fa.sharedSizeBytes;
     const size_t per_wg = stat + dyn_lds;
@@ -1404,13 +1407,25 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                             // below 3 waves/SIMD, where the 2-wave build (no spills) is faster
                             // (config C: 6.53 vs 7.41 s)
                             const bool eu2 = !kx && !mesh_only &&
-                                             (c->knobs.ci_eu == 2 || (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes)));
+                                             (c->knobs.ci_eu == 2 ||
+                                              (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes, Gc > 1)));
                             c->ci_wps = (kx || eu2) ? 2 : 3;
-                            auto kern1 = kx ? k_chain_ci<1, 0, true>
-                                         : mesh_only ? k_chain_ci<1, -1>
-                                         : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true> : k_chain_ci<1, 0, false, 0, true>)
-                                         : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2> : k_chain_ci<1, 64, false, 2>)
-                                               : (lds_nodes ? k_chain_ci<1> : k_chain_ci<1, 64>);
+                            // one tile per wave: the group's state in scalar registers;
+                            // several (opts.lanes_per_wave): the per-lane kMulti instantiations.
+                            // The one-wave kX chain runs the per-lane code at one tile per wave
+                            // too (lanes_per_tile = 64): with the scalar state config G measured
+                            // 473.5 against 471.5 ms (profiles/chain_sgpr/), so kX has no other
+                            // one-wave instantiation
+                            auto kern1 = kx ? k_chain_ci<1, 0, true, 0, false, true>
+                                : Gc > 1
+                                ? (mesh_only ? k_chain_ci<1, -1, false, 0, false, true>
+                                   : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true, true> : k_chain_ci<1, 0, false, 0, true, true>)
+                                   : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2, false, true> : k_chain_ci<1, 64, false, 2, false, true>)
+                                         : (lds_nodes ? k_chain_ci<1, 0, false, 0, false, true> : k_chain_ci<1, 64, false, 0, false, true>))
+                                : (mesh_only ? k_chain_ci<1, -1>
+                                   : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true> : k_chain_ci<1, 0, false, 0, true>)
+                                   : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2> : k_chain_ci<1, 64, false, 2>)
+                                         : (lds_nodes ? k_chain_ci<1> : k_chain_ci<1, 64>));
                             hipLaunchKernelGGL(kern1, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave),
                                                lds, st, with_slot(sc, 2), rp, lw, c->d_jump, c->wb, sb,
                                                nb, kWave / Gc, ring, c->d_ctr, Gc == 1 ? ord : nullptr,

@@ -8,6 +8,7 @@
 #include "k_chain_1.hip"
 #include "k_chain_n.hip"
 #include "k_chain_x.hip"
+#include "k_chain_g.hip"
 #include "k_paths_m.hip"
 #include "k_paths_x.hip"
 #include "k_serial.hip"
