@@ -167,11 +167,11 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     const uint64_t inc = pcg_inc_of((uint64_t)tile_of_slot(rp, slot_base + (bs < nslots_batch ? bs : 0)));
 #ifdef PBRT_CI_DIAG   // diagnostics build (make diag): steps, lane-0 phase clocks, on-chain D histogram
     unsigned long long steps = 0, busy = 0;
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long ph_cyc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tprev = clock64();
     auto mark = [&](int k) {
         long long now = clock64();
-        ph[k] += (unsigned long long)(now - tprev);
+        ph_cyc[k] += (unsigned long long)(now - tprev);
         tprev = now;
     };
     if (tid < 64) dh[tid] = 0;
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     // lane trajectory state
     uint32_t off = kNoOff;
     // the pixel the lane's candidate belongs to: the group's current pixel, or
-    // (kNps) the next. Without kNps a pixel's end drops every candidate (5), so
+    // (kNps) the next. Without kNps a pixel's end drops every candidate (2), so
     // a live candidate is always of the current pixel and the lane keeps none
     int opi_r = -1;
     // kX: the trajectory's throughput, etaScale and start state live in LDS
@@ -260,252 +260,104 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     ray.tmax = kInf;
     ray.time = 0;
 
-    for (;;) {
-        // ---- (1) groups that need a pixel: StartPixel + bounce 1, one group at a time
-        for (int q = 0; q < G; q++) {
-            while (gs[q].phase == 0) {
-                const int64_t bq = blk * G + q;
-                const int64_t tile = tile_of_slot(rp, slot_base + bq);
-                const uint64_t incq = pcg_inc_of((uint64_t)tile);
-                const int64_t pi = gs[q].pi;
-                const int64_t rec = bq * wb.ppt + pi;
-                int64_t x0, y0, x1, y1;
-                tile_bounds(rp, tile, x0, y0, x1, y1);
-                const int64_t px = x0 + pi % (x1 - x0), py = y0 + pi / (x1 - x0);
-                double* gs1d = wb.s1d + rec * wb.s1d_stride;
-                double* sp = s1d ? s1d : gs1d;
-                const uint64_t S1 = start_pixel_wave<kSpWin>(rp, J, gs[q].S, incq, sp, other, vbuf, &sh_state, &sh_draws);
-                if (s1d)
-                    for (int idx = tid; idx < ndims * n; idx += kT) gs1d[idx] = s1d[idx];
-                // the first traced sample's camera time value (read before the ring
-                // clear: with one tile per workgroup the StartPixel staging aliases the ring)
-                const double time_u = sp[1 < n ? 1 : 0];
-                __syncthreads();
-                // next-pixel speculation already filled this pixel's ring (kNps)
-                const bool spec_ran = nps_on && gs[q].nps != 0;
-                if (!spec_ran) {
-                    RingEnt* rq = nps_on ? ring_of(pi) : (RingEnt*)(lds + lay.ring) + (size_t)q * R;
-                    for (uint32_t i = (uint32_t)tid; i < R; i += kT) rq[i].tag = kNoOff;
-                }
-                // bounce 1 (camera ray, first hit, BSDF) was computed for every
-                // pixel record by k_wf_primary; only the ray time needs StartPixel
-                PixelRec& pr = wb.prec[rec];
-                const int hit0 = pr.hit, panic0 = pr.panic0;
-                if (tid == 0) {   // pbrt_gpu_cancel: every group of the workgroup ends
-                    if (prog)   // the heartbeat k_gate tells running chains from undispatched ones by
-                        __hip_atomic_fetch_add(&prog[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    const uint64_t now = wall_clock64();
-                    const bool host = now - last_host_poll >= 100000;   // 1 ms at 100 MHz
-                    if (host) last_host_poll = now;
-                    if (cancel_requested(sc, host))
-                        for (int q2 = 0; q2 < G; q2++) gs[q2].phase = 2;
-                }
-                if (tid == 0 && gs[q].phase == 0) {
-                    if (hit0)   // the camera ray's time (Get1D after pFilm, pLens) of the pixel's first traced sample
-                        pr.si.time = camera_ray(cam, (double)px, (double)py, time_u, V2{0.0, 0.0}).time;
-                    ChainCache& pq = pcs[2 * q + rpar(pi)];
-                    pq.si = pr.si;
-                    pq.b = pr.b;
-                    if constexpr (kX) pq.x = pr.x;
-                    pq.wo = pr.wo;
-                    pq.hit = hit0;
-                    CiGroup& s = gs[q];
-                    s.S = S1;
-                    s.A += sh_draws;   // the first traced sample starts after StartPixel's draws
-                    s.head = s.A;
-                    // (a first sample below the speculation's base: dense issue from the head)
-                    s.nxt = (spec_ran && s.A >= s.nb) ? max(s.nnx, s.A) : s.A;
-                    if (!spec_ran) {
-                        if (rpar(pi)) s.rb1 = s.A;
-                        else s.rb0 = s.A;
-                    }
-                    s.nps = 0;
-                    s.kh = 1;
-                    s.reissue = 0;
-                    wb.tile_npx[bq] = (int32_t)(pi + 1);
-                    if (panic0) {   // the first traced sample panics at bounce 1: the tile ends here
-                        s.phase = 2;
-                    } else if (hit0) {
-                        s.phase = 1;
-                    } else {   // no traced bounce: every sample is black and draws only its
-                        // CameraSample's PCG32 values (n_dims < 2: pLens; c_camera)
-                        if (ndims < 2) {
-                            s.S = pcg_advance(J, S1, incq, (uint64_t)(n - 1) * camera_draws(ndims));
-                            s.A += (uint32_t)(n - 1) * camera_draws(ndims);
-                        }
-                        s.pi = pi + 1;
-                        s.phase = s.pi < s.npx ? 0 : 2;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-        mark(0);
-        bool any_chain = false;
-        for (int q = 0; q < G; q++) any_chain |= gs[q].phase == 1;
-        if (!any_chain) break;
-        CI_DIAG(steps++;)
+    // The group's state as the issue (4) read it, with the pixel record and the
+    // sampler that go with it: the scatter (5) and the next iteration's traversal
+    // (1) and walk (2) use this copy (the issue changes only nxt, nnx and reissue
+    // in gs, which none of them reads from it); the walk and StartPixel then
+    // change gs, and (4) reads it again. Wave-uniform, in scalar registers,
+    // unless kMulti.
+    CiGroup sg;
+    if constexpr (kMulti) sg = gs[g];
+    else sg = uni(gs[0]);
+    int64_t rec = bs * wb.ppt + sg.pi;
+    SpecSampler ss{wb.s1d + rec * wb.s1d_stride, n, ndims, kX && wb.rrb ? wb.rrb + bs * kCiMaxRing : nullptr};
 
-        // ---- (2) idle lanes take the next offsets of their group
-        CiGroup sg;
-        if constexpr (kMulti) sg = gs[g];
-        else sg = uni(gs[0]);
-        const int64_t rec = bs * wb.ppt + sg.pi;
-        const SpecSampler ss{wb.s1d + rec * wb.s1d_stride, n, ndims,
-                             kX && wb.rrb ? wb.rrb + bs * kCiMaxRing : nullptr};
-        {
-            const bool idle = sg.phase == 1 && off == kNoOff;
-            const unsigned long long m = __ballot(idle) & gmask;
-            int nidle = __popcll(m);
-            int rank;
-            if constexpr (kMulti) rank = __popcll(m & ((1ULL << lane) - 1ULL));
-            else rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (kW > 1) {   // rank the idle lanes across the tile's waves
-                if (lane == 0) wcnt[wv] = nidle;
-                __syncthreads();
-                int before = 0, tot = 0;
-                for (int w = 0; w < kW; w++) {
-                    const int cw = wcnt[w];
-                    before += w < wv ? cw : 0;
-                    tot += cw;
-                }
-                rank += before;
-                nidle = tot;
-            }
-            const int re = (sg.reissue && nidle > 0) ? 1 : 0;
-            const uint32_t nx0 = sg.nxt;
-            // offsets < head + R keep the ring collision-free
-            const int avail = nx0 < sg.head + R ? (int)((sg.head + R - nx0 + cs - 1) / cs) : 0;
-#if PBRT_CI_TAILCAP
-            const uint32_t tail = sg.head + (uint32_t)(n - 1 - sg.kh) * dmax;
-            const int capn = nx0 <= tail ? (int)((tail - nx0) / cs) + 1 : 0;
-            int nspec = min(min(nidle - re, avail), capn);
-            if (kStats && zcap > 0.0f && sg.dcnt >= kNpsMinStats) {
-                // the current pixel's last sample starts near head + rem * mean: a cap
-                // zcap sigmas above it (the lanes beyond go to the next pixel, or idle)
-                const float rem = (float)(n - 1 - sg.kh);
-                const float mu = sg.dsum / (float)sg.dcnt;
-                const float sd = sqrtf(fmaxf(0.0f, sg.dsq / (float)sg.dcnt - mu * mu));
-                const uint32_t scap = sg.head + (uint32_t)(rem * mu + zcap * sd * sqrtf(rem));
-                nspec = min(nspec, nx0 <= scap ? (int)((scap - nx0) / cs) + 1 : 0);
-            }
-#else
-            const int nspec = min(nidle - re, avail);
-#endif
-            // the lanes left: the next pixel's candidates (stride 1, within its ring's window)
-            int nspec1 = 0;
-            if (kNps && sg.phase == 1 && sg.nps) {
-                const int avail1 = sg.nnx < sg.nb + R ? (int)(sg.nb + R - sg.nnx) : 0;
-                nspec1 = max(0, min(nidle - re - max(nspec, 0), avail1));
-            }
-            uint32_t o = kNoOff;
-            bool exact = false;
-            int opix = (int)sg.pi;
-            if (idle) {
-                if (re && rank == 0) {
-                    o = sg.head;
-                    exact = true;
-                } else {
-                    rank -= re;
-                    if (rank < nspec) {
-                        o = nx0 + cs * (uint32_t)rank;
-                    } else if (kNps && rank - nspec < nspec1) {
-                        o = sg.nnx + (uint32_t)(rank - nspec);
-                        opix = (int)sg.pi + 1;
-                    }
-                }
-            }
-            if (gl == 0 && sg.phase == 1) {
-                gs[g].nxt = nx0 + cs * (uint32_t)max(nspec, 0);
-                if (kNps) gs[g].nnx = sg.nnx + (uint32_t)nspec1;
-                CI_DIAG(ph[5] += (unsigned long long)(max(nspec, 0) + nspec1 + re);)   // candidate trajectories issued
-                CI_DIAG(ph[7] += (unsigned long long)nspec1;)   // of them next-pixel speculation
-                if (re) gs[g].reissue = 0;
-            }
-            if (o != kNoOff) {
-                off = o;
-                if (kNps) opi_r = opix;
-                RingEnt& e = ring_of(opix)[(off - (rpar(opix) ? sg.rb1 : sg.rb0)) & (R - 1u)];
-                if constexpr (kStIssue) {
-                    const uint64_t st = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
-                    e.st = st;
-                    c.rng.state = st;
-                } else {
-                    st0 = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
-                    c.rng.state = st0;
-                }
-                c.draws = 0;
-                c_camera(c, ndims);   // camera: Get2D pFilm, Get2D pLens, Get1D time
-                c.k = exact ? sg.kh : -1;
-                c.kdep = 0;
-                if constexpr (kX) {   // speculative: RR decisions on stratified values are recorded
-                    c.rri = (!exact && ss.rrb) ? (int)((off - sg.rb0) & (R - 1u)) : -1;
-                    c.rrn = 0;
-                }
-                beta = spec(1);
-                eta_scale = 1.0;
-                bounces = 1;
-                const ChainCache& pc = pcs[2 * g + rpar(opix)];
-                const int r = traj_scatter<kX>(sc, pc.si, pc.b, pc.x, pc.wo, c, ss, beta, eta_scale, bounces, ray,
-                                               rp.max_depth, rp.rr_threshold);
-                tracing = r == 0;
-                if (r != 0) {
-                    if constexpr (!kStIssue) e.st = st0;
-                    e.d = ring_d<kX>(c, ss, r == 1 ? c.draws : (c.k >= 0 ? kBadExactD : kBadSpecD));
-                    e.tag = off;
-                    off = kNoOff;
-                }
-            }
-        }
+    // One scatter per iteration (Matte analytic and kX kernels). An iteration is
+    // (1) traversal, (2) walk and drop, (3) StartPixel, (4) issue, (5) scatter: a
+    // lane goes issue -> scatter -> traversal -> (walk) -> hit processing +
+    // scatter -> traversal ..., and the scatter of a lane just issued and that
+    // of a lane whose ray hit are the same code, run once for both (config B
+    // 349.8 -> 340.1 ms, G 471.9 -> 462.8). A trajectory that ends inside the
+    // scatter then leaves its lane idle for one traversal: the lane is issued
+    // again in (4) of the next iteration, after that iteration's (1). The
+    // mesh-only and the windowed-StartPixel kernels therefore keep the order
+    // (3), (4) + scatter of the lanes just issued, (1) + hit processing +
+    // scatter, (2), in which such a lane traverses again at once: with the one
+    // scatter config D measured 660.8 -> 673.4 ms and C 4207 -> 4333 ms
+    // (profiles/chain_one_scatter/).
+    constexpr bool kOneScatter = kDepth >= 0 && !kSpWin;
+    using Both = std::integral_constant<int, 0>;    // the scatter's lanes: just issued and pending hits,
+    using Fresh = std::integral_constant<int, 1>;   // just issued only,
+    using Hits = std::integral_constant<int, 2>;    // pending hits only
+    int best = -1;   // a lane's pending hit, from the traversal to the scatter
+    V3 ph{0, 0, 0};
+    // ---- (1) every live trajectory's ray: a miss or a panic ends it here, a hit
+    // keeps only the primitive and the hit point until the scatter
+    auto traverse = [&]() __attribute__((always_inline)) {
         const int64_t opi = kNps ? (int64_t)opi_r : sg.pi;
-        mark(1);
-        CI_DIAG(const unsigned long long tbusy = __ballot(tracing); if (lane == 0) busy += (unsigned long long)__popcll(tbusy);)
-        // ---- (3) one bounce of every live trajectory
+        best = -1;
+        int panic = 0;
 #ifdef PBRT_CI_DENSE_WALK   // experiment build: the whole wave walks together (dense leaf tests)
         const bool dense = kDepth == 0 && sc.dense_ok && sc.use_lds_nodes;
-        int panic = 0, best = -1;
-        V3 ph{0, 0, 0};
         if (dense) bvh_walk_dense(sc, ray, tracing, panic, best, ph, dense_lds + (size_t)wv * kDenseScratch);
         if (tracing) {
             if (!dense) bvh_walk<false, kT, PBRT_CHAIN_LB, (kDepth < 0)>(sc, ray, stack, panic, best, ph);
 #else
         if (tracing) {
-            int panic = 0, best;
-            V3 ph;
             bvh_walk<false, kT, PBRT_CHAIN_LB, (kDepth < 0)>(sc, ray, stack, panic, best, ph);
 #endif
-            mark(2);
-            uint32_t d = kNoOff;
-            if (panic) {
-                d = c.k >= 0 ? kBadExactD : kBadSpecD;
-            } else if (best < 0) {
-                d = c.draws;
-            } else {
-                SI si;
-                prim_si(sc, best, ray, ph, si);
-                BSDF b;
-                BSDFX x;
-                if ((kX ? compute_bsdf_x(sc, si, b, x) : compute_bsdf(sc, si, b)) < 0) {
-                    d = c.k >= 0 ? kBadExactD : kBadSpecD;
-                } else {
-                    const int r = traj_scatter<kX>(sc, si, b, x, ray.d, c, ss, beta, eta_scale, bounces, ray,
-                                                   rp.max_depth, rp.rr_threshold);
-                    if (r == 1) d = c.draws;
-                    else if (r == 2) d = c.k >= 0 ? kBadExactD : kBadSpecD;
-                }
-            }
-            if (d != kNoOff) {
+            if (panic || best < 0) {
                 RingEnt& e = ring_of(opi)[(off - (rpar(opi) ? sg.rb1 : sg.rb0)) & (R - 1u)];
                 if constexpr (!kStIssue) e.st = st0;
-                e.d = ring_d<kX>(c, ss, d);
+                e.d = ring_d<kX>(c, ss, panic ? (c.k >= 0 ? kBadExactD : kBadSpecD) : c.draws);
                 e.tag = off;
                 off = kNoOff;
                 tracing = false;
             }
         }
-        mark(3);
+    };
+    // ---- the scatter of the lanes just issued (the interaction and BSDF of their
+    // pixel's bounce 1, from its ChainCache) and of the lanes whose ray hit
+    auto scatter = [&](auto which, bool fresh) __attribute__((always_inline)) {
+        constexpr int kWhich = decltype(which)::value;
+        const bool first = kWhich == Fresh::value ? true : kWhich == Hits::value ? false : fresh;
+        if (kWhich == Fresh::value ? fresh : kWhich == Hits::value ? tracing : (fresh || tracing)) {
+            const int64_t spi = kNps ? (int64_t)opi_r : sg.pi;   // the lane's pixel
+            SI si;
+            BSDF b;
+            BSDFX x;
+            // (read before the branch: a load of ray.d at its end is merged with the
+            // ChainCache's into one load through either address, and the ray lands in scratch)
+            V3 wo = ray.d;
+            bool ok = true;
+            if (first) {
+                const ChainCache& pc = pcs[2 * g + rpar(spi)];
+                si = pc.si;
+                b = pc.b;
+                if constexpr (kX) x = pc.x;
+                wo = pc.wo;
+            } else {
+                prim_si(sc, best, ray, ph, si);
+                ok = (kX ? compute_bsdf_x(sc, si, b, x) : compute_bsdf(sc, si, b)) >= 0;
+            }
+            const int r = !ok ? 2
+                              : traj_scatter<kX>(sc, si, b, x, wo, c, ss, beta, eta_scale, bounces, ray, rp.max_depth,
+                                                 rp.rr_threshold);
+            tracing = r == 0;
+            if (r != 0) {
+                RingEnt& e = ring_of(spi)[(off - (rpar(spi) ? sg.rb1 : sg.rb0)) & (R - 1u)];
+                if constexpr (!kStIssue) e.st = st0;
+                e.d = ring_d<kX>(c, ss, r == 1 ? c.draws : (c.k >= 0 ? kBadExactD : kBadSpecD));
+                e.tag = off;
+                off = kNoOff;
+            }
+        }
+    };
+    // ---- (2) barrier, the leaders' walk, the next pixel's ring clear, the drop
+    auto walk_drop = [&]() __attribute__((always_inline)) {
+        const int64_t opi = kNps ? (int64_t)opi_r : sg.pi;
         __syncthreads();
-        // ---- (4) each group leader walks its chain through the ring
+        // each group leader walks its chain through the ring
         if (gl == 0 && sg.phase == 1) {
             // (per lane: the walk's state depends on the ring entries it loads, and
             // reading the copy through scalar registers saved no VGPR in any build)
@@ -550,7 +402,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 CI_DIAG(atomicAdd(&dh[min(d / 2u, 63u)], 1u);)
                 // the tail cap's bound (dmax per sample): an on-chain D above it would
                 // only slow the chain, never change a result; counted so tests can pin it
-                CI_DIAG(if (d > dmax) ph[6]++;)
+                CI_DIAG(if (d > dmax) ph_cyc[6]++;)
                 CI_DIAG(if (d & 1u) atomicAdd(&ctr->odd_d, 1ull);)
                 if (kStats) {   // the tile's draw-count statistics
                     s.dcnt++;
@@ -634,7 +486,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 pc.hit = pn.hit;
             }
         }
-        // ---- (5) drop candidates the chain has left behind
+        // drop candidates the chain has left behind, a pending hit with them
         if (off != kNoOff) {
             const CiGroup s2 = gs[g];
             bool keep = false;
@@ -650,15 +502,229 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 tracing = false;
             }
         }
-        mark(4);
+    };
+
+    for (;;) {
+        if constexpr (kOneScatter) {
+            CI_DIAG(const unsigned long long tbusy = __ballot(tracing); if (lane == 0) busy += (unsigned long long)__popcll(tbusy);)
+            traverse();
+            mark(2);
+            walk_drop();
+            mark(4);
+        }
+        // ---- (3) groups that need a pixel: StartPixel + bounce 1, one group at a time
+        for (int q = 0; q < G; q++) {
+            while (gs[q].phase == 0) {
+                const int64_t bq = blk * G + q;
+                const int64_t tile = tile_of_slot(rp, slot_base + bq);
+                const uint64_t incq = pcg_inc_of((uint64_t)tile);
+                const int64_t pi = gs[q].pi;
+                const int64_t rec = bq * wb.ppt + pi;
+                int64_t x0, y0, x1, y1;
+                tile_bounds(rp, tile, x0, y0, x1, y1);
+                const int64_t px = x0 + pi % (x1 - x0), py = y0 + pi / (x1 - x0);
+                double* gs1d = wb.s1d + rec * wb.s1d_stride;
+                double* sp = s1d ? s1d : gs1d;
+                // (inlined here in every instantiation: as a call, the windowed StartPixel of
+                // the multi-wave kernels takes rp through scratch, 80 -> 192 B/lane)
+                uint64_t S1;
+                [[clang::always_inline]] S1 = start_pixel_wave<kSpWin>(rp, J, gs[q].S, incq, sp, other, vbuf, &sh_state, &sh_draws);
+                if (s1d)
+                    for (int idx = tid; idx < ndims * n; idx += kT) gs1d[idx] = s1d[idx];
+                // the first traced sample's camera time value (read before the ring
+                // clear: with one tile per workgroup the StartPixel staging aliases the ring)
+                const double time_u = sp[1 < n ? 1 : 0];
+                __syncthreads();
+                // next-pixel speculation already filled this pixel's ring (kNps)
+                const bool spec_ran = nps_on && gs[q].nps != 0;
+                if (!spec_ran) {
+                    RingEnt* rq = nps_on ? ring_of(pi) : (RingEnt*)(lds + lay.ring) + (size_t)q * R;
+                    for (uint32_t i = (uint32_t)tid; i < R; i += kT) rq[i].tag = kNoOff;
+                }
+                // bounce 1 (camera ray, first hit, BSDF) was computed for every
+                // pixel record by k_wf_primary; only the ray time needs StartPixel
+                PixelRec& pr = wb.prec[rec];
+                const int hit0 = pr.hit, panic0 = pr.panic0;
+                if (tid == 0) {   // pbrt_gpu_cancel: every group of the workgroup ends
+                    if (prog)   // the heartbeat k_gate tells running chains from undispatched ones by
+                        __hip_atomic_fetch_add(&prog[2], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    const uint64_t now = wall_clock64();
+                    const bool host = now - last_host_poll >= 100000;   // 1 ms at 100 MHz
+                    if (host) last_host_poll = now;
+                    if (cancel_requested(sc, host))
+                        for (int q2 = 0; q2 < G; q2++) gs[q2].phase = 2;
+                }
+                if (tid == 0 && gs[q].phase == 0) {
+                    if (hit0)   // the camera ray's time (Get1D after pFilm, pLens) of the pixel's first traced sample
+                        pr.si.time = camera_ray(cam, (double)px, (double)py, time_u, V2{0.0, 0.0}).time;
+                    ChainCache& pq = pcs[2 * q + rpar(pi)];
+                    pq.si = pr.si;
+                    pq.b = pr.b;
+                    if constexpr (kX) pq.x = pr.x;
+                    pq.wo = pr.wo;
+                    pq.hit = hit0;
+                    CiGroup& s = gs[q];
+                    s.S = S1;
+                    s.A += sh_draws;   // the first traced sample starts after StartPixel's draws
+                    s.head = s.A;
+                    // (a first sample below the speculation's base: dense issue from the head)
+                    s.nxt = (spec_ran && s.A >= s.nb) ? max(s.nnx, s.A) : s.A;
+                    if (!spec_ran) {
+                        if (rpar(pi)) s.rb1 = s.A;
+                        else s.rb0 = s.A;
+                    }
+                    s.nps = 0;
+                    s.kh = 1;
+                    s.reissue = 0;
+                    wb.tile_npx[bq] = (int32_t)(pi + 1);
+                    if (panic0) {   // the first traced sample panics at bounce 1: the tile ends here
+                        s.phase = 2;
+                    } else if (hit0) {
+                        s.phase = 1;
+                    } else {   // no traced bounce: every sample is black and draws only its
+                        // CameraSample's PCG32 values (n_dims < 2: pLens; c_camera)
+                        if (ndims < 2) {
+                            s.S = pcg_advance(J, S1, incq, (uint64_t)(n - 1) * camera_draws(ndims));
+                            s.A += (uint32_t)(n - 1) * camera_draws(ndims);
+                        }
+                        s.pi = pi + 1;
+                        s.phase = s.pi < s.npx ? 0 : 2;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+        mark(0);
+        bool any_chain = false;
+        for (int q = 0; q < G; q++) any_chain |= gs[q].phase == 1;
+        if (!any_chain) break;
+        CI_DIAG(steps++;)
+
+        // ---- (4) idle lanes take the next offsets of their group
+        if constexpr (kMulti) sg = gs[g];
+        else sg = uni(gs[0]);
+        rec = bs * wb.ppt + sg.pi;
+        ss.s1d = wb.s1d + rec * wb.s1d_stride;
+        bool fresh = false;   // the lane took an offset in this iteration
+        {
+            const bool idle = sg.phase == 1 && off == kNoOff;
+            const unsigned long long m = __ballot(idle) & gmask;
+            int nidle = __popcll(m);
+            int rank;
+            if constexpr (kMulti) rank = __popcll(m & ((1ULL << lane) - 1ULL));
+            else rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+            if (kW > 1) {   // rank the idle lanes across the tile's waves
+                if (lane == 0) wcnt[wv] = nidle;
+                __syncthreads();
+                int before = 0, tot = 0;
+                for (int w = 0; w < kW; w++) {
+                    const int cw = wcnt[w];
+                    before += w < wv ? cw : 0;
+                    tot += cw;
+                }
+                rank += before;
+                nidle = tot;
+            }
+            const int re = (sg.reissue && nidle > 0) ? 1 : 0;
+            const uint32_t nx0 = sg.nxt;
+            // offsets < head + R keep the ring collision-free
+            const int avail = nx0 < sg.head + R ? (int)((sg.head + R - nx0 + cs - 1) / cs) : 0;
+#if PBRT_CI_TAILCAP
+            const uint32_t tail = sg.head + (uint32_t)(n - 1 - sg.kh) * dmax;
+            const int capn = nx0 <= tail ? (int)((tail - nx0) / cs) + 1 : 0;
+            int nspec = min(min(nidle - re, avail), capn);
+            if (kStats && zcap > 0.0f && sg.dcnt >= kNpsMinStats) {
+                // the current pixel's last sample starts near head + rem * mean: a cap
+                // zcap sigmas above it (the lanes beyond go to the next pixel, or idle)
+                const float rem = (float)(n - 1 - sg.kh);
+                const float mu = sg.dsum / (float)sg.dcnt;
+                const float sd = sqrtf(fmaxf(0.0f, sg.dsq / (float)sg.dcnt - mu * mu));
+                const uint32_t scap = sg.head + (uint32_t)(rem * mu + zcap * sd * sqrtf(rem));
+                nspec = min(nspec, nx0 <= scap ? (int)((scap - nx0) / cs) + 1 : 0);
+            }
+#else
+            const int nspec = min(nidle - re, avail);
+#endif
+            // the lanes left: the next pixel's candidates (stride 1, within its ring's window)
+            int nspec1 = 0;
+            if (kNps && sg.phase == 1 && sg.nps) {
+                const int avail1 = sg.nnx < sg.nb + R ? (int)(sg.nb + R - sg.nnx) : 0;
+                nspec1 = max(0, min(nidle - re - max(nspec, 0), avail1));
+            }
+            uint32_t o = kNoOff;
+            bool exact = false;
+            int opix = (int)sg.pi;
+            if (idle) {
+                if (re && rank == 0) {
+                    o = sg.head;
+                    exact = true;
+                } else {
+                    rank -= re;
+                    if (rank < nspec) {
+                        o = nx0 + cs * (uint32_t)rank;
+                    } else if (kNps && rank - nspec < nspec1) {
+                        o = sg.nnx + (uint32_t)(rank - nspec);
+                        opix = (int)sg.pi + 1;
+                    }
+                }
+            }
+            if (gl == 0 && sg.phase == 1) {
+                gs[g].nxt = nx0 + cs * (uint32_t)max(nspec, 0);
+                if (kNps) gs[g].nnx = sg.nnx + (uint32_t)nspec1;
+                CI_DIAG(ph_cyc[5] += (unsigned long long)(max(nspec, 0) + nspec1 + re);)   // candidate trajectories issued
+                CI_DIAG(ph_cyc[7] += (unsigned long long)nspec1;)   // of them next-pixel speculation
+                if (re) gs[g].reissue = 0;
+            }
+            if (o != kNoOff) {
+                off = o;
+                if (kNps) opi_r = opix;
+                RingEnt& e = ring_of(opix)[(off - (rpar(opix) ? sg.rb1 : sg.rb0)) & (R - 1u)];
+                if constexpr (kStIssue) {
+                    const uint64_t st = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
+                    e.st = st;
+                    c.rng.state = st;
+                } else {
+                    st0 = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
+                    c.rng.state = st0;
+                }
+                c.draws = 0;
+                c_camera(c, ndims);   // camera: Get2D pFilm, Get2D pLens, Get1D time
+                c.k = exact ? sg.kh : -1;
+                c.kdep = 0;
+                if constexpr (kX) {   // speculative: RR decisions on stratified values are recorded
+                    c.rri = (!exact && ss.rrb) ? (int)((off - sg.rb0) & (R - 1u)) : -1;
+                    c.rrn = 0;
+                }
+                beta = spec(1);
+                eta_scale = 1.0;
+                bounces = 1;
+                fresh = true;
+            }
+        }
+        if constexpr (kOneScatter) {
+            mark(1);
+            // ---- (5) one scatter, for the lanes just issued and the lanes whose ray hit
+            scatter(Both{}, fresh);
+            mark(3);
+        } else {
+            scatter(Fresh{}, fresh);
+            mark(1);
+            CI_DIAG(const unsigned long long tbusy = __ballot(tracing); if (lane == 0) busy += (unsigned long long)__popcll(tbusy);)
+            traverse();
+            mark(2);
+            scatter(Hits{}, false);
+            mark(3);
+            walk_drop();
+            mark(4);
+        }
     }
 #ifdef PBRT_CI_DIAG
     __syncthreads();
     if (tid < 64 && dh[tid]) atomicAdd(&ctr->dhist[tid], (unsigned long long)dh[tid]);
     if (tid == 0) {
         atomicAdd(&ctr->windows, steps);
-        for (int k = 0; k < 8; k++) atomicAdd(&ctr->phase[k], ph[k]);
-        atomicAdd(&ctr->nps_issued, ph[7]);
+        for (int k = 0; k < 8; k++) atomicAdd(&ctr->phase[k], ph_cyc[k]);
+        atomicAdd(&ctr->nps_issued, ph_cyc[7]);
     }
     if (lane == 0) atomicAdd(&ctr->busy, busy);
 #endif

@@ -7,6 +7,11 @@ With the diagnostics build (make diag) it also prints, per pixel, the chain
 steps, the candidate trajectories issued and the on-chain ones (the on-chain
 D histogram's total), and the count of on-chain draw counts above the tail
 cap's bound dmax (k_chain.h; must be 0).
+
+The lane-0 phase clocks follow k_chain.h's mark(): StartPixel, issue, traversal,
+hit processing + scatter, barrier + walk + drop. The kernels with one scatter per
+step run the scatter of the lanes just issued in "hit_scatter"; the mesh and the
+windowed-StartPixel kernels run it with the issue, as every kernel did before.
 """
 import argparse
 import ctypes as C
@@ -40,7 +45,7 @@ else:
     scene = {"readme": G.Scene.readme, "readme_glass": G.Scene.readme_glass, "cornell": G.Scene.cornell}[a.scene](
         a.width, a.height)
 names = ["paths", "camera_samples", "closest_rays", "shadow_rays", "any_panic", "windows",
-         "cyc_start_pixel", "cyc_issue_first_scatter", "cyc_traversal", "cyc_hit_processing",
+         "cyc_start_pixel", "cyc_issue", "cyc_traversal", "cyc_hit_scatter",
          "cyc_barrier_walk", "issued", "d_over_dmax", "cyc_7"]
 with G.Renderer(scene, kernel=a.kernel, occupancy=a.occupancy, lanes_per_wave=a.tiles_per_wave) as r:
     rd = abi.render_desc(a.spp, a.spp, max_depth=a.max_depth, tile_begin=a.tile_begin, tile_stride=a.tile_stride)
