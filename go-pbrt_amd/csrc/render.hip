@@ -12,7 +12,11 @@
 //                    tile's RNG-offset chain), k_paths_ci or the path
 //                    wavefront k_pw_* (full paths), k_film (tile films);
 //                    THROUGHPUT mode: k_mb_setup instead of the chain.
-//   k_dl_*           DirectLighting: pixel-order StartPixel + jump-ahead, one
+//   camera-start route  (PBRT_KERNEL_WAVE_CAM, opt-in) the wave pipeline for
+//                    renders whose camera ray belongs to the sample (n_dims 0,
+//                    or 1 with a thin lens): k_chain_cam, k_paths_cam,
+//                    k_film_cam; THROUGHPUT mode: k_cam_setup instead of the chain.
+//   k_dl_*         DirectLighting: pixel-order StartPixel + jump-ahead, one
 //                    lane per sample.
 //   k_merge_film     Film.MergeFilmTile (film.go:115-132): per output pixel,
 //                    RGBToXYZ of every covering tile film in tile-index order.
@@ -201,6 +205,8 @@ struct pbrt_gpu_ctx {
     bool use_ci = false;   // the Path chain stage (k_chain_ci)
     bool use_dl = false;   // DirectLighting on k_dl_setup / k_dl_samples
     ChainLayout lay_ci{};
+    bool use_cam = false;   // the camera-start route (PBRT_KERNEL_WAVE_CAM: k_chain_cam, k_paths_cam, k_film_cam)
+    ChainLayout lay_cam{};
     // device scene
     pbrt_shape_desc* d_shapes = nullptr;
     pbrt_material_desc* d_materials = nullptr;
@@ -722,6 +728,56 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
     return L.total <= 48 * 1024;
 }
 
+// Can the camera-start route (PBRT_KERNEL_WAVE_CAM) replay this render exactly?
+// It takes the renders whose camera ray belongs to the sample: n_dims == 0, or
+// n_dims == 1 with a thin lens (cam_sample.h). Path integrator, Matte scenes on an
+// LDS-staged tree; otherwise wave_eligible's conditions. `why` names the reason
+// of a refusal. L: k_chain_cam's / k_cam_setup's dynamic LDS (the StartPixel
+// staging of n_dims == 1, aliased with the offset ring).
+bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const RenderParams& rp, ChainLayout& L,
+                       std::string& why) {
+    auto no = [&](const char* m) {
+        why = m;
+        return false;
+    };
+    if (rd->flags & PBRT_FLAG_PANIC_FIDELITY) return no("panic fidelity runs on the serial kernel");
+    if (rd->integrator != PBRT_INTEGRATOR_PATH) return no("Path integrator only (DirectLighting is out of scope)");
+    if (rd->max_depth > 2048) return no("maxDepth > 2048");
+    if (rd->n_dims >= 2) return no("n_dims >= 2: the camera ray is the pixel's (the wave_ci route)");
+    if (rd->n_dims == 1 && !(c->host_scene.camera.lens_radius > 0))
+        return no("n_dims == 1 with a pinhole: the camera ray is the pixel's (the wave_ci route)");
+    if (c->non_matte) return no("Mirror / Glass / OrenNayar materials");
+    if (c->mesh.n_nodes != 0) return no("triangle meshes");
+    if (c->host_scene.n_nodes > kLdsNodes) return no("a tree of more than 64 nodes");
+    const int nl = c->host_scene.n_lights;
+    if (nl > kMaxCachedLights) return no("more than 16 lights");
+    if (nl > 0) {
+        const pbrt_distribution_desc& d = c->host_dist;
+        if (!(d.func_int > 0)) return no("a light with pdf 0");
+        for (int i = 0; i < d.count; i++)
+            if (!(d.func[i] > 0)) return no("a light with pdf 0");   // it changes the draw count
+    }
+    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->lds_per_block)
+        return no("the tile film does not fit LDS");
+    const int64_t n = rp.spp, nd = rp.ndims;
+    if (n > 4096 || nd * n > 8192) return no("more than 4096 samples per pixel");
+    int64_t off = 0;
+    auto put = [&](int64_t bytes) {
+        int64_t o = off;
+        off += (bytes + 15) & ~int64_t(15);
+        return (int)o;
+    };
+    L = ChainLayout{};
+    // (large spp: the serial StartPixel writes straight to the pixel's global record)
+    L.s1d = rp.sp_serial || nd == 0 ? -1 : put(nd * n * 8);
+    L.other = put(rp.sp_serial ? 16 : nd * n * 2 + 16);
+    L.vbuf = put(rp.sp_serial ? 4 : sp_vbuf_bytes(rp));
+    L.staging = (int)off;
+    L.ring = 0;
+    L.total = std::max((int)off, kCiRingBytes);
+    return true;
+}
+
 // k_chain_ci's LDS layout for w waves per tile and G tiles per wave. With one
 // tile per workgroup (G == 1) the StartPixel staging aliases the offset ring:
 // a group starts a pixel only after its chain has dropped every candidate,
@@ -1060,7 +1116,15 @@ int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
                        c->mesh.n_nodes == 0 &&
                        (int64_t)rp.ndims * n * 4 + kSpRing * 4 <= PBRT_SP_WINDOW_KB * 1024 ? 1 : 0;
     }
-    c->use_spec = c->kernel_req != PBRT_KERNEL_SERIAL && wave_eligible(c, rd, rp, c->lay, c->lay_ci);
+    // the camera-start route is opt-in (AUTO keeps its renders on the serial kernel)
+    c->use_cam = false;
+    if (c->kernel_req == PBRT_KERNEL_WAVE_CAM) {
+        std::string why;
+        if (!wave_cam_eligible(c, rd, rp, c->lay_cam, why))
+            return set_err(c, PBRT_E_UNSUPPORTED, "render not eligible for the camera-start wave kernels: " + why);
+        c->use_cam = true;
+    }
+    c->use_spec = !c->use_cam && c->kernel_req != PBRT_KERNEL_SERIAL && wave_eligible(c, rd, rp, c->lay, c->lay_ci);
     if ((c->kernel_req == PBRT_KERNEL_WAVE || c->kernel_req == PBRT_KERNEL_WAVEFRONT ||
          c->kernel_req == PBRT_KERNEL_WAVE_CI) && !c->use_spec)
         return set_err(c, PBRT_E_UNSUPPORTED, "render not eligible for the wave-parallel kernels");
@@ -1072,6 +1136,10 @@ int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
     // the chain stage of the wave pipeline is k_chain_ci (PBRT_KERNEL_WAVE and
     // _WAVEFRONT, whose window and wavefront chains it replaced, select it too)
     c->use_ci = c->use_spec && !c->use_dl;
+    if (c->use_cam && rp.n_slots > 0) {
+        int rcw = wave_buffers(c);
+        if (rcw != PBRT_OK) return rcw;
+    }
     if (c->use_spec && rp.n_slots > 0) {
         int rcw = wave_buffers(c);
         if (rcw != PBRT_OK) return rcw;
@@ -1114,7 +1182,7 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
     }
     if (opts && (opts->occupancy == 2 || opts->occupancy == 4 || opts->occupancy == 8)) c->min_waves = opts->occupancy;
     if (opts) c->occ_req = opts->occupancy;
-    if (opts && (opts->kernel < PBRT_KERNEL_AUTO || opts->kernel > PBRT_KERNEL_WAVE_DL)) {
+    if (opts && (opts->kernel < PBRT_KERNEL_AUTO || opts->kernel > PBRT_KERNEL_WAVE_CAM)) {
         delete c;
         return PBRT_E_INVALID;
     }
@@ -1240,6 +1308,97 @@ int pbrt_gpu_render_async_into(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, doub
 }
 
 namespace {
+// The camera-start route (PBRT_KERNEL_WAVE_CAM), per batch on the one stream:
+// k_chain_cam (EXACT; THROUGHPUT: k_cam_setup), k_paths_cam, then the tile films
+// (k_film_cam's per-sample footprints with n_dims == 0, else k_film) and
+// k_panic_reduce. No kernel waits on another's progress (no k_gate). A context
+// that has rendered the configuration launches the chain heaviest tile first
+// (the chain times of its last frame); a cold frame runs in launch order: there
+// is no bounce-1 record for k_tile_cost to probe from.
+int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
+    const RenderParams& rp = c->rp;
+    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
+    c->last_kernel = PBRT_KERNEL_WAVE_CAM;
+    c->n_batches = (int)((rp.n_slots + c->wave_batch - 1) / c->wave_batch);
+    while ((int)c->bev.size() < 3 * c->n_batches) {
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreate(&e));
+        c->bev.push_back(e);
+    }
+    c->ov_done = 0;
+    c->probed = false;
+    for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
+        const int64_t nb = std::min<int64_t>(c->wave_batch, rp.n_slots - sb);
+        const int64_t nrec = nb * c->wb.ppt;
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
+        if (mb) {
+            const int64_t blocks = rp.ndims > 0 ? nrec : (nrec + kWave - 1) / kWave;
+            hipLaunchKernelGGL(k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
+                               with_slot(sc, 4), rp, c->lay_cam, c->d_jump, c->wb, sb, nb);
+        } else {
+            const uint32_t* order = nullptr;
+            uint32_t* ticks = nullptr;
+            if (c->n_batches == 1 && ci_order_enabled(c)) {
+                if (c->ticks_cap < nb) {
+                    if (c->d_ticks) (void)hipFree(c->d_ticks);
+                    if (c->d_slot_order) (void)hipFree(c->d_slot_order);
+                    c->d_ticks = c->d_slot_order = nullptr;
+                    c->ticks_cap = 0;
+                    HIPCHK(c, hipMalloc((void**)&c->d_ticks, sizeof(uint32_t) * (size_t)nb * kTickPlanes));
+                    HIPCHK(c, hipMalloc((void**)&c->d_slot_order, sizeof(uint32_t) * (size_t)nb));
+                    c->ticks_cap = nb;
+                }
+                const uint64_t key = schedule_key(rp, -1);   // (-1: no k_chain_ci launch has this wave count)
+                bool cached = false;
+                if (!(c->order_key == key && (int64_t)c->h_slot_order.size() == nb) && ci_order_cache(c)) {
+                    SchedEntry e;   // a fresh context: another context's measured order for this scene
+                    if (sched_cache_get(c, key, nb, e)) {
+                        c->h_slot_order = std::move(e.order);
+                        c->order_key = key;
+                        cached = true;
+                    }
+                }
+                if (c->order_key == key && (int64_t)c->h_slot_order.size() == nb) {
+                    c->sched_src = cached ? PBRT_SCHED_CACHED : PBRT_SCHED_LEARNED;
+                    HIPCHK(c, hipMemcpyAsync(c->d_slot_order, c->h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
+                                             hipMemcpyHostToDevice, c->stream));
+                    order = c->d_slot_order;
+                }
+                if (kTickPlanes > 1)  // diagnostics builds read start / end clocks this kernel does not record
+                    HIPCHK(c, hipMemsetAsync(c->d_ticks, 0, sizeof(uint32_t) * (size_t)nb * kTickPlanes, c->stream));
+                ticks = c->d_ticks;
+                c->ticks_pending = true;
+                c->ticks_key = key;
+                c->ticks_n = nb;
+                c->h_slot_kw.assign((size_t)nb, (uint8_t)1);
+                c->ci_wps = 3;
+            }
+            hipLaunchKernelGGL(k_chain_cam, dim3((unsigned)nb), dim3(kWave), (unsigned)c->lay_cam.total, c->stream,
+                               with_slot(sc, 2), rp, c->lay_cam, c->d_jump, c->wb, sb, nb, order, ticks);
+        }
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
+        if (rp.spp > 1) {
+            // pixels per wave: about 256 (pixel, sample) work items, so that the lanes stay
+            // filled at a few samples per pixel too
+            const int m = rp.spp - 1, pp = m >= 32 ? 4 : m >= 8 ? 16 : 64;
+            auto kern = mb ? (pp == 4 ? k_paths_cam<4, true> : pp == 16 ? k_paths_cam<16, true> : k_paths_cam<64, true>)
+                           : (pp == 4 ? k_paths_cam<4, false> : pp == 16 ? k_paths_cam<16, false> : k_paths_cam<64, false>);
+            hipLaunchKernelGGL(kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
+                               with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
+        }
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
+        if (rp.ndims == 0)
+            hipLaunchKernelGGL(mb ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)nb), dim3(kFilmThreads), 0,
+                               c->stream, c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
+        else
+            hipLaunchKernelGGL(k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
+                               c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
+        hipLaunchKernelGGL(k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, sb, nb,
+                           c->d_panics, c->d_ctr);
+    }
+    return PBRT_OK;
+}
+
 int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_device) {
     HIPCHK(c, hipSetDevice(c->device));
     c->t_start = std::chrono::steady_clock::now();
@@ -1256,7 +1415,10 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (rp.n_slots > 0) {
         DevScene sc = dev_scene(c, rd->integrator == PBRT_INTEGRATOR_PATH);
-        if (c->use_spec) {
+        if (c->use_cam) {
+            const int rcc = enqueue_cam(c, sc);
+            if (rcc != PBRT_OK) return rcc;
+        } else if (c->use_spec) {
             c->last_kernel = c->use_dl ? PBRT_KERNEL_WAVE_DL
                              : rp.mode == PBRT_MODE_THROUGHPUT ? PBRT_KERNEL_WAVE : PBRT_KERNEL_WAVE_CI;
             const bool lds_nodes = c->host_scene.n_nodes <= kLdsNodes;

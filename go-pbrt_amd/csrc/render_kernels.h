@@ -41,6 +41,13 @@ __global__ void k_order_of_keys(const uint64_t* __restrict__ keys, int64_t nb, u
 __global__ void k_gate(const uint32_t* __restrict__ prog, uint32_t b, uint32_t e, Counters* __restrict__ ctr);
 template <int kW, int kDepth = 0, bool kX = false, int kEu = 0, bool kSpWin = false, bool kMulti = false>
 __global__ void k_chain_ci(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, int lanes_per_tile, int ring_size, Counters* __restrict__ ctr, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks, int cstride, uint32_t* __restrict__ prog);
+// the camera-start wave route (PBRT_KERNEL_WAVE_CAM): k_chain_c.hip, k_paths_c.hip
+__global__ void k_chain_cam(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks);
+__global__ void k_cam_setup(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch);
+template <int P, bool kMB>
+__global__ void k_paths_cam(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template <bool kMB>
+__global__ void k_film_cam(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, double* __restrict__ films, const int* __restrict__ cancel_seen, Counters* __restrict__ ctr);
 __global__ void k_merge_film(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, const double* __restrict__ films, double* __restrict__ out, const int* __restrict__ cancel_seen);
 __global__ void k_merge_film_group(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, pbrtgroup::GroupMap gm, GroupFilms films, double* __restrict__ out);
 __global__ void k_intersect(DevScene sc, int64_t n, const double* __restrict__ rays, double* __restrict__ out, int any_hit);

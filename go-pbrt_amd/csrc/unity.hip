@@ -11,6 +11,8 @@
 #include "k_chain_g.hip"
 #include "k_paths_m.hip"
 #include "k_paths_x.hip"
+#include "k_chain_c.hip"
+#include "k_paths_c.hip"
 #include "k_serial.hip"
 #include "k_pw.hip"
 #include "k_frame.hip"

@@ -305,8 +305,20 @@ typedef struct pbrt_gpu_opts {
  *  WAVE_DL    DirectLighting (n_dims >= 1): pixel-order StartPixel +
  *             jump-ahead, one lane per sample;
  *  WAVE, WAVEFRONT  (round 1's window and wavefront chains, since replaced)
- *             request the wave pipeline; st.kernel reports WAVE_CI.
- * THROUGHPUT mode reports WAVE for the wave pipeline (no chain). */
+ *             request the wave pipeline; st.kernel reports WAVE_CI;
+ *  WAVE_CAM   the wave pipeline for renders whose camera ray belongs to the
+ *             sample, not to the pixel: n_dims == 0 (Stratified without sampled
+ *             dimensions, pbrt_random_sampler; pinhole or thin lens) or
+ *             n_dims == 1 with a thin lens. Path integrator, Matte scenes on
+ *             trees of <= 64 nodes, every light pdf > 0. Every trajectory of
+ *             the chain (k_chain_cam) and every path (k_paths_cam) starts at
+ *             the camera; with n_dims == 0 the film footprint is per sample
+ *             (k_film_cam). Opt-in: AUTO keeps such renders on SERIAL, and
+ *             anything else requested with WAVE_CAM is PBRT_E_UNSUPPORTED
+ *             (DirectLighting, n_dims >= 2, n_dims == 1 with a pinhole,
+ *             Mirror / Glass / OrenNayar, meshes, larger trees, panic fidelity).
+ * THROUGHPUT mode reports WAVE for the wave pipeline (no chain), and WAVE_CAM
+ * for a WAVE_CAM request. */
 /* WAVE kernel: always replay StartPixel serially (the path normally taken
  * only after a pcg_bounded rejection); results are identical. */
 #define PBRT_FLAG_SERIAL_START_PIXEL 1
@@ -318,7 +330,8 @@ typedef struct pbrt_gpu_opts {
 
 enum { PBRT_KERNEL_AUTO = 0, PBRT_KERNEL_SERIAL = 1, PBRT_KERNEL_WAVE = 2, PBRT_KERNEL_WAVEFRONT = 3,
        PBRT_KERNEL_WAVE_CI = 4, /* wave pipeline, continuous-issue offset chain */
-       PBRT_KERNEL_WAVE_DL = 5  /* DirectLighting: pixel-order StartPixel + jump-ahead, one lane per sample */ };
+       PBRT_KERNEL_WAVE_DL = 5, /* DirectLighting: pixel-order StartPixel + jump-ahead, one lane per sample */
+       PBRT_KERNEL_WAVE_CAM = 6 /* wave pipeline with per-sample camera rays (n_dims 0, or 1 with a thin lens); opt-in */ };
 
 typedef struct pbrt_gpu_ctx pbrt_gpu_ctx;
 

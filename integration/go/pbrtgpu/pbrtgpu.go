@@ -201,12 +201,27 @@ type Renderer struct {
 	bufs map[*DeviceBuffer]struct{} // its open device buffers (NewDeviceBuffer)
 }
 
+// Kernel requests (pbrt_gpu_opts.kernel). KernelAuto picks per render;
+// KernelWaveCam opts renders with per-sample camera rays (WithRandomSampler,
+// nDims 0, or nDims 1 with a thin lens; Path, Matte scenes) into the wave
+// pipeline, which KernelAuto keeps on the serial kernel.
+const (
+	KernelAuto    = int32(C.PBRT_KERNEL_AUTO)
+	KernelWaveCam = int32(C.PBRT_KERNEL_WAVE_CAM)
+)
+
 func NewRenderer(s *SceneBuilder, device int) (*Renderer, error) {
+	return NewRendererKernel(s, device, KernelAuto)
+}
+
+// NewRendererKernel is NewRenderer with a kernel request (Kernel*).
+func NewRendererKernel(s *SceneBuilder, device int, kernel int32) (*Renderer, error) {
 	if s.desc == nil {
 		return nil, fmt.Errorf("pbrtgpu: scene not built")
 	}
 	var opts C.pbrt_gpu_opts
 	opts.device = C.int32_t(device)
+	opts.kernel = C.int32_t(kernel)
 	var ctx *C.pbrt_gpu_ctx
 	if rc := C.pbrt_gpu_create(s.desc, &opts, &ctx); rc != C.PBRT_OK {
 		return nil, fmt.Errorf("pbrt_gpu_create: status %d", int(rc))
