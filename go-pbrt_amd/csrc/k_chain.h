@@ -58,6 +58,13 @@ __device__ __forceinline__ CiGroup uni(const CiGroup& s) {
     u.dsq = uni(s.dsq);
     return u;
 }
+__device__ __forceinline__ CiGroupC uni(const CiGroupC& s) {
+    CiGroupC u;
+    static_cast<CiGroup&>(u) = uni(static_cast<const CiGroup&>(s));
+    u.Sn = uni(s.Sn);
+    u.Sq = uni(s.Sq);
+    return u;
+}
 
 template <int kW, int kDepth, bool kX, int kEu, bool kSpWin, bool kMulti>
 // kDepth < 0 (kCiMeshOnly): scenes of triangle meshes only, no analytic walk
@@ -91,7 +98,10 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     // bvh_walk_dense's per-wave scratch (LDS-staged trees only)
     __shared__ __attribute__((aligned(16))) unsigned char dense_lds[kDepth > 0 ? 16 : kW * kDenseScratch];
 #endif
-    __shared__ CiGroup gs[kCiMaxGroups];
+    // the groups' state; one tile per workgroup: one group, with the states it
+    // carries at nxt and nnx (kCarry below)
+    using Group = std::conditional_t<kMulti, CiGroup, CiGroupC>;
+    __shared__ Group gs[kMulti ? kCiMaxGroups : 1];
     __shared__ uint64_t sh_state;
     __shared__ uint32_t sh_draws;   // StartPixel's draw count
     __shared__ int sh_act;          // next-pixel speculation started this step
@@ -182,7 +192,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
 #endif
     if (tid < G) {
         const int64_t b = blk * G + tid;
-        CiGroup& s = gs[tid];
+        Group& s = gs[tid];
         s.pi = 0;
         s.kh = 1;
         s.A = s.head = s.nxt = 0;
@@ -192,6 +202,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         s.dcnt = 0;
         s.dsum = s.dsq = 0.0f;
         s.reissue = 0;
+        if constexpr (!kMulti) s.Sn = s.Sq = 0;
         if (b < nslots_batch) {
             int64_t x0, y0, x1, y1;
             tile_bounds(rp, tile_of_slot(rp, slot_base + b), x0, y0, x1, y1);
@@ -234,6 +245,16 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     // the walk reads it only under the tag the lane sets last), so the lane does
     // not carry it through the trajectory
     constexpr bool kStIssue = !kMulti;
+    // One tile per workgroup: the group carries the states at nxt and nnx (Sn,
+    // Sq), so the issue positions a lane with one table step (pcg_step) from its
+    // wave's base and not with a jump from A. The per-lane jump was a divergent
+    // loop of about ten scalar-load round trips and 40 multiplier instructions
+    // per step, 8.8% of the one-wave Matte chain's lane-0 cycles (config B 343.3
+    // -> 336.3 ms, C 4138 -> 4036 ms, D, G and a 1/8 shard level; DESIGN §7,
+    // profiles/chain_issue_table/). With several tiles per wave the group's
+    // state is per lane and the jump stays.
+    constexpr bool kCarry = !kMulti;
+    static_assert(!kCarry || kStIssue, "the carried states rely on ring entries that hold their state from the issue on");
     __shared__ uint64_t xs_st0[kLdsState && !kStIssue ? kT : 1];
     uint64_t st0_r = 0;
     Spec beta_r = spec(1);
@@ -266,7 +287,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
     // in gs, which none of them reads from it); the walk and StartPixel then
     // change gs, and (4) reads it again. Wave-uniform, in scalar registers,
     // unless kMulti.
-    CiGroup sg;
+    Group sg;
     if constexpr (kMulti) sg = gs[g];
     else sg = uni(gs[0]);
     int64_t rec = bs * wb.ppt + sg.pi;
@@ -370,6 +391,11 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
             }
             RingEnt* rcur = ring_of(s.pi);
             const uint32_t rbase = rpar(s.pi) ? s.rb1 : s.rb0;
+            // kCarry: the last walked entry's draw count. The state at head is that
+            // entry's, dl draws on (the issue wrote it, and no offset in flight maps
+            // to its slot before the head has passed head + R)
+            uint32_t dl = 0;
+            bool walked = false;
             for (; s.phase == 1;) {
                 RingEnt& e = rcur[(s.head - rbase) & (R - 1u)];
                 if (e.tag != s.head) break;
@@ -411,15 +437,25 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 }
                 s.kh++;
                 s.head += d;
+                dl = d;
+                walked = true;
                 if (s.kh >= n) {   // every sample of the pixel has its offset; the next StartPixel starts here
-                    s.S = pcg_advance(J, s.S, inc, (uint64_t)(s.head - s.A));
+                    if constexpr (kCarry) s.S = pcg_advance_near(J, e.st, inc, (uint64_t)d);
+                    else s.S = pcg_advance(J, s.S, inc, (uint64_t)(s.head - s.A));
                     s.A = s.head;
                     s.pi++;
                     s.phase = s.pi < s.npx ? 0 : 2;
                     break;
                 }
             }
-            if (s.nxt < s.head || (cs == 2u && ((s.nxt ^ s.head) & 1u))) s.nxt = s.head;
+            if (s.nxt < s.head || (cs == 2u && ((s.nxt ^ s.head) & 1u))) {
+                // the chain overtook the issue, or D was odd (stride 2): issue from the head
+                s.nxt = s.head;
+                if constexpr (kCarry)
+                    if (s.phase == 1)
+                        gs[g].Sn = walked ? pcg_advance_near(J, rcur[(s.head - dl - rbase) & (R - 1u)].st, inc, (uint64_t)dl)
+                                      : pcg_advance(J, s.S, inc, (uint64_t)(s.head - s.A));
+            }
             // speculate on the next pixel: when the last sample has its offset (its
             // first traced sample then starts at least StartPixel's events past this
             // one), or, with the tile's draw-count statistics, from rp.ci_nps samples
@@ -441,6 +477,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                     s.nps = 1;
                     s.nb = s.head + (uint32_t)lo + (uint32_t)rp.sp_events;
                     s.nnx = s.nb;
+                    if constexpr (kNps) gs[g].Sq = pcg_advance_near(J, s.S, inc, (uint64_t)(s.nb - s.A));
                     if (rpar(s.pi + 1)) s.rb1 = s.nb;
                     else s.rb0 = s.nb;
                     act = 1;
@@ -474,7 +511,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
         if (kNps && tid == 0 && !(gl == 0 && sg.phase == 1)) sh_act = 0;
         __syncthreads();
         if (kNps && sh_act) {   // the next pixel's ring (its parity's: the pixel before this one's) and ChainCache
-            const CiGroup s3 = uni(gs[0]);   // (kNps: one tile per workgroup)
+            const CiGroup s3 = uni(static_cast<const CiGroup&>(gs[0]));   // (kNps: one tile per workgroup)
             RingEnt* rn = ring_of(s3.pi + 1);
             for (uint32_t i = (uint32_t)tid; i < R; i += kT) rn[i].tag = kNoOff;
             if (tid == 0) {
@@ -563,12 +600,13 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                     if constexpr (kX) pq.x = pr.x;
                     pq.wo = pr.wo;
                     pq.hit = hit0;
-                    CiGroup& s = gs[q];
+                    Group& s = gs[q];
                     s.S = S1;
                     s.A += sh_draws;   // the first traced sample starts after StartPixel's draws
                     s.head = s.A;
                     // (a first sample below the speculation's base: dense issue from the head)
                     s.nxt = (spec_ran && s.A >= s.nb) ? max(s.nnx, s.A) : s.A;
+                    if constexpr (kCarry) s.Sn = s.nxt == s.A ? S1 : s.Sq;   // (nxt is A or the speculation's nnx)
                     if (!spec_ran) {
                         if (rpar(pi)) s.rb1 = s.A;
                         else s.rb0 = s.A;
@@ -611,6 +649,7 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
             const unsigned long long m = __ballot(idle) & gmask;
             int nidle = __popcll(m);
             int rank;
+            int wbefore = 0;   // idle lanes of the tile's waves before this one (kW > 1)
             if constexpr (kMulti) rank = __popcll(m & ((1ULL << lane) - 1ULL));
             else rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
             if (kW > 1) {   // rank the idle lanes across the tile's waves
@@ -622,8 +661,13 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                     before += w < wv ? cw : 0;
                     tot += cw;
                 }
+                if constexpr (kCarry) {   // (LDS loads: wave-uniform, for the scalar base updates below)
+                    before = uni(before);
+                    tot = uni(tot);
+                }
                 rank += before;
                 nidle = tot;
+                wbefore = before;
             }
             const int re = (sg.reissue && nidle > 0) ? 1 : 0;
             const uint32_t nx0 = sg.nxt;
@@ -651,9 +695,27 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 const int avail1 = sg.nnx < sg.nb + R ? (int)(sg.nb + R - sg.nnx) : 0;
                 nspec1 = max(0, min(nidle - re - max(nspec, 0), avail1));
             }
+            // kCarry: the states the candidates are stepped from, all on wave-uniform
+            // operands (scalar). The tile's ranks run through its waves: this wave's
+            // first candidate has rank r0, r0c of them before it are the current
+            // pixel's (bases nxt, Sn) and r0q the next pixel's (nnx, Sq), so every
+            // lane of the wave is fewer than 64 candidates from the wave's base
+            const int ns = max(nspec, 0);
+            const int r0 = max(wbefore - re, 0), r0c = min(r0, ns), r0q = r0 - r0c;
+            uint64_t wSn = 0, wSq = 0, nSn = 0, nSq = 0;
+            if constexpr (kCarry) {
+                wSn = nSn = sg.Sn;
+                wSq = nSq = sg.Sq;
+                if (ns > 0) nSn = pcg_advance_near(J, sg.Sn, inc, (uint64_t)(cs * (uint32_t)ns));
+                if (kNps && nspec1 > 0) nSq = pcg_advance_near(J, sg.Sq, inc, (uint64_t)nspec1);
+                if (kW > 1 && r0c > 0) wSn = pcg_advance_near(J, sg.Sn, inc, (uint64_t)(cs * (uint32_t)r0c));
+                if (kNps && r0q > 0 && nspec1 > 0) wSq = pcg_advance_near(J, sg.Sq, inc, (uint64_t)r0q);
+            }
             uint32_t o = kNoOff;
             bool exact = false;
             int opix = (int)sg.pi;
+            uint32_t kst = 0;        // kCarry: the lane's candidate is kst draws past
+            uint64_t wbase = wSn;    // its wave's base wbase
             if (idle) {
                 if (re && rank == 0) {
                     o = sg.head;
@@ -662,15 +724,20 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                     rank -= re;
                     if (rank < nspec) {
                         o = nx0 + cs * (uint32_t)rank;
+                        kst = cs * (uint32_t)(rank - r0c);
                     } else if (kNps && rank - nspec < nspec1) {
                         o = sg.nnx + (uint32_t)(rank - nspec);
                         opix = (int)sg.pi + 1;
+                        kst = (uint32_t)(rank - nspec - r0q);
+                        wbase = wSq;
                     }
                 }
             }
             if (gl == 0 && sg.phase == 1) {
                 gs[g].nxt = nx0 + cs * (uint32_t)max(nspec, 0);
+                if constexpr (kCarry) gs[g].Sn = nSn;
                 if (kNps) gs[g].nnx = sg.nnx + (uint32_t)nspec1;
+                if constexpr (kNps) gs[g].Sq = nSq;
                 CI_DIAG(ph_cyc[5] += (unsigned long long)(max(nspec, 0) + nspec1 + re);)   // candidate trajectories issued
                 CI_DIAG(ph_cyc[7] += (unsigned long long)nspec1;)   // of them next-pixel speculation
                 if (re) gs[g].reissue = 0;
@@ -679,8 +746,14 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
                 off = o;
                 if (kNps) opi_r = opix;
                 RingEnt& e = ring_of(opix)[(off - (rpar(opix) ? sg.rb1 : sg.rb0)) & (R - 1u)];
-                if constexpr (kStIssue) {
-                    const uint64_t st = pcg_advance(J, sg.S, inc, (uint64_t)(o - sg.A));
+                if constexpr (kCarry) {
+                    // The re-issued head: its entry still holds the state its first issue
+                    // wrote (the walk cleared only the tag, and no other offset in flight
+                    // maps to the slot). One wave: rank <= 63 and cs <= 2 keep kst in the
+                    // table; across waves the helper's other paths stay behind it.
+                    const uint64_t st = exact    ? e.st
+                                        : kW == 1 ? pcg_step(J, wbase, inc, kst)
+                                                  : pcg_advance_near(J, wbase, inc, (uint64_t)kst);
                     e.st = st;
                     c.rng.state = st;
                 } else {

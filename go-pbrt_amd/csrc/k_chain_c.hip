@@ -43,6 +43,7 @@ struct CamGroup {
     uint32_t A;      // absolute offset of S
     uint32_t head;   // offset of sample kh
     uint32_t nxt;    // next offset to issue
+    uint64_t Sn;     // PCG32 state at nxt, moved with it (k_chain_ci's carried state, k_chain.h kCarry)
     int kh;          // next sample without an offset
     int phase;       // 0 needs a pixel, 1 resolving offsets, 2 tile finished
     int px, py;      // the current pixel's raster coordinates
@@ -84,6 +85,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
         gs.pi = 0;
         gs.npx = (x1 - x0) * (y1 - y0);
         gs.A = gs.head = gs.nxt = 0;
+        gs.Sn = 0;
         gs.kh = 1;
         gs.phase = (gs.npx > 0 && n > 1) ? 0 : 2;   // sample 0 is never traced (#2): one sample, no path
         gs.px = gs.py = 0;
@@ -155,6 +157,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
                 if (cancel_requested(sc, host)) s.phase = 2;
             }
             const int64_t rec = bs * wb.ppt + s.pi;
+            // the last walked entry's draw count: the state at head is that entry's, dl draws on
+            uint32_t dl = 0;
+            bool walked = false;
             for (; s.phase == 1;) {
                 const RingEnt& e = ring[s.head & (R - 1u)];
                 if (e.tag != s.head) break;
@@ -167,15 +172,22 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
                 }
                 s.kh++;
                 s.head += d;
+                dl = d;
+                walked = true;
                 if (s.kh >= n) {   // every sample of the pixel has its offset
-                    s.S = pcg_advance(J, s.S, inc, (uint64_t)(s.head - s.A));
+                    s.S = pcg_advance_near(J, e.st, inc, (uint64_t)d);
                     s.A = s.head;
                     s.pi++;
                     s.phase = s.pi < s.npx ? 0 : 2;
                     break;
                 }
             }
-            if (s.nxt < s.head) s.nxt = s.head;
+            if (s.nxt < s.head) {   // the chain overtook the issue
+                s.nxt = s.head;
+                if (s.phase == 1)
+                    gs.Sn = walked ? pcg_advance_near(J, ring[(s.head - dl) & (R - 1u)].st, inc, (uint64_t)dl)
+                                   : pcg_advance(J, s.S, inc, (uint64_t)(s.head - s.A));
+            }
             gs.S = s.S;
             gs.A = s.A;
             gs.pi = s.pi;
@@ -222,6 +234,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
                 gs.S = S1;
                 gs.A += sp_draws;
                 gs.head = gs.nxt = gs.A;
+                gs.Sn = S1;
                 gs.kh = 1;
                 gs.px = (int)(x0 + pi % (x1 - x0));
                 gs.py = (int)(y0 + pi / (x1 - x0));
@@ -233,9 +246,9 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
 
         // ---- (4) idle lanes take the next offsets, draw their camera sample and join the next traversal
         {
-            const uint32_t head = uni(gs.head), nx0 = uni(gs.nxt), A = uni(gs.A);
+            const uint32_t head = uni(gs.head), nx0 = uni(gs.nxt);
             const int kh = uni(gs.kh);
-            const uint64_t S = uni(gs.S);
+            const uint64_t Sn = uni(gs.Sn);
             const int px = uni(gs.px), py = uni(gs.py);
             const bool idle = off == kNoOff;
             const unsigned long long m = __ballot(idle);
@@ -246,10 +259,16 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
             const uint32_t tail = head + (uint32_t)(n - 1 - kh) * dmax;
             const int capn = nx0 <= tail ? (int)(tail - nx0) + 1 : 0;
             const int nspec = min(min(nidle, avail), capn);
-            if (tid == 0) gs.nxt = nx0 + (uint32_t)nspec;
+            // the state at nxt moves with it (wave-uniform operands: scalar); a lane's
+            // state is one table step from it (rank <= 63)
+            const uint64_t nSn = nspec > 0 ? pcg_advance_near(J, Sn, inc, (uint64_t)nspec) : Sn;
+            if (tid == 0) {
+                gs.nxt = nx0 + (uint32_t)nspec;
+                gs.Sn = nSn;
+            }
             if (idle && rank < nspec) {
                 off = nx0 + (uint32_t)rank;
-                uint64_t st = pcg_advance(J, S, inc, (uint64_t)(off - A));
+                uint64_t st = pcg_step(J, Sn, inc, (uint32_t)rank);
                 ring[off & (R - 1u)].st = st;
                 const pbrtcam::CamSample cs = pbrtcam::cam_sample(st, inc, ndims);
                 c.rng.state = st;

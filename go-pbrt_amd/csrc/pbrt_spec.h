@@ -27,20 +27,12 @@
 #pragma clang fp contract(off)
 
 #include "pbrt_path.h"
+#include "pcg_jump.h"
 #include <type_traits>
 
 namespace pbrt {
 
-// PCG32 jump-ahead: state after 2^i steps = a[i] * state + inc * b[i] (mod 2^64)
-struct PcgJump {
-    uint64_t a[64];
-    uint64_t b[64];
-};
-__device__ __forceinline__ uint64_t pcg_advance(const PcgJump& J, uint64_t s, uint64_t inc, uint64_t n) {
-    for (int i = 0; n; ++i, n >>= 1)
-        if (n & 1) s = J.a[i] * s + inc * J.b[i];
-    return s;
-}
+// PCG32 jump-ahead (PcgJump, pcg_advance, pcg_step, pcg_advance_near): pcg_jump.h
 __device__ __forceinline__ uint32_t pcg_output(uint64_t old) {   // rng.go:36-42 (#1)
     uint32_t xs = (uint32_t)(((old >> 18) ^ old) >> 27);
     uint32_t rot = (uint32_t)(old >> 59);
@@ -365,9 +357,26 @@ __device__ inline int traj_scatter(const DevScene& sc, const SI& isect, const BS
                                    Cursor& c, const SpecSampler& ss, Spec& beta, double& eta_scale, int& bounces,
                                    Ray& ray, int max_depth, double rr_threshold) {
     if ((kX ? bsdfx_nonspecular(b, x) : b.n_bxdfs > 0) && sc.n_lights > 0) {   // UniformSampleOneLight's draws
+#ifdef PBRT_TRAJ_SKIP_MAP
+        // experiment build: the PCG32 draws among the five unused values (a
+        // stratified dimension consumes none) as one constant-coefficient map.
+        // Measured and not kept: config B 336.3 -> 339.5 ms (DESIGN §7,
+        // profiles/chain_issue_table/); the count is a per-lane value, the
+        // five steps it replaces were straight-line code
+        int k = 0;
+        if (c.cur1d < ss.ndims) c.cur1d++;
+        else k += 1;
+        for (int i = 0; i < 2; i++) {
+            if (c.cur2d < ss.ndims) c.cur2d++;
+            else k += 2;
+        }
+        c.draws += (uint32_t)k;
+        c.rng.state = pcg_skip(c.rng.state, c.rng.inc, k);
+#else
         c_skip1d(c, ss);
         c_get2d(c, ss);
         c_get2d(c, ss);
+#endif
     }
     V2 u = c_get2d(c, ss);
     V3 wi;

@@ -616,13 +616,7 @@ int validate_scene(const pbrt_scene_desc* s) {
 const PcgJump& pcg_jump_table() {
     static PcgJump J = [] {
         PcgJump t;
-        uint64_t a = 0x5851f42d4c957f2dULL, b = 1;   // one step: s' = a*s + inc*1
-        for (int i = 0; i < 64; i++) {
-            t.a[i] = a;
-            t.b[i] = b;
-            b = b * (a + 1);   // two applications of the 2^i jump
-            a = a * a;
-        }
+        pcg_jump_fill(t);   // pcg_jump.h
         return t;
     }();
     return J;

@@ -884,5 +884,13 @@ struct CiGroup {
     uint32_t dcnt;      // on-chain draw counts seen in the tile (kNps: their mean and spread set the
     float dsum, dsq;    // current pixel's speculation cap and when the next pixel's starts)
 };
+// One tile per workgroup (k_chain_ci without kMulti): the group also carries
+// the PCG32 states at nxt and (next-pixel speculation) at nnx, moved with them,
+// so an idle lane's state is one table step from its wave's base (pcg_step) and
+// no jump from A. (Its own type: the kernels with several tiles per wave keep
+// four groups in LDS and do not use the two states.)
+struct CiGroupC : CiGroup {
+    uint64_t Sn, Sq;
+};
 
 }  // namespace pbrtk
