@@ -5,6 +5,7 @@
 
 #include <string>
 
+#include "launch_log.h"
 #include "pbrt_mesh.h"
 
 namespace pbrt {
@@ -25,12 +26,14 @@ struct MeshBuild {
 };
 
 // Builds the meshes of `s` on the current device (stream `st`, synchronous).
-// Returns PBRT_OK, or a pbrt_status with `err` set.
-int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std::string& err);
+// Returns PBRT_OK, or a pbrt_status with `err` set. `log` (may be null) records the launches.
+int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std::string& err, LaunchLog* log = nullptr);
 void mesh_bvh_free(MeshBuild& b);
 
 // Ascending bitonic sort of npad 64-bit keys on stream `st` (npad a power of
 // two >= 2048; pad with ~0). Also orders k_chain_ci's cold-frame schedule.
-void bitonic_sort_u64(uint64_t* keys, uint32_t npad, hipStream_t st);
+void bitonic_sort_u64(uint64_t* keys, uint32_t npad, hipStream_t st, LaunchLog* log = nullptr);
+// The unit's kernels by host function pointer, for pbrt_gpu_launch_log.
+const KernelName* mesh_bvh_kernel_names(size_t* n);
 
 }  // namespace pbrt

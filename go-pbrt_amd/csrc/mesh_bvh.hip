@@ -319,6 +319,8 @@ __global__ __launch_bounds__(kB) void k_flatten(int n, const int32_t* __restrict
 // in ascending centre order along the axis of their centres' largest spread;
 // the level's inner slots get consecutive indices after the level (atomic
 // counter), so the tree is laid out level by level, siblings together.
+// (compiled only into the builds that launch it)
+#if PBRT_MESH_WIDE
 __global__ __launch_bounds__(kB) void k_collapse(int n, const int32_t* __restrict__ cl, const int32_t* __restrict__ cr,
                                                  const float* __restrict__ box, const int32_t* __restrict__ tc,
                                                  const int32_t* __restrict__ ht, int32_t* __restrict__ bin_of,
@@ -396,6 +398,17 @@ __global__ __launch_bounds__(kB) void k_collapse(int n, const int32_t* __restric
     nd.pad = 0;
     out[i] = nd;
 }
+#endif
+
+// the names pbrt_gpu_launch_log gives this unit's kernels
+const KernelName kMeshKernelNames[] = {
+    PBRT_KERNEL_NAME(k_centroids), PBRT_KERNEL_NAME(k_morton), PBRT_KERNEL_NAME(k_bitonic_global),
+    PBRT_KERNEL_NAME(k_bitonic_local), PBRT_KERNEL_NAME(k_gather), PBRT_KERNEL_NAME(k_karras),
+    PBRT_KERNEL_NAME(k_up), PBRT_KERNEL_NAME(k_flatten),
+#if PBRT_MESH_WIDE
+    PBRT_KERNEL_NAME(k_collapse),
+#endif
+};
 
 template <class T>
 hipError_t dmalloc(T** p, size_t n) {
@@ -404,14 +417,19 @@ hipError_t dmalloc(T** p, size_t n) {
 
 }  // namespace
 
+const KernelName* mesh_bvh_kernel_names(size_t* n) {
+    *n = sizeof(kMeshKernelNames) / sizeof(kMeshKernelNames[0]);
+    return kMeshKernelNames;
+}
+
 // stages k <= 2048 sort each 2048-key block in LDS (one launch); later
 // stages: global passes for strides >= 2048, then the rest in LDS
-void bitonic_sort_u64(uint64_t* keys, uint32_t npad, hipStream_t st) {
-    hipLaunchKernelGGL(k_bitonic_local, dim3(npad / 2048), dim3(1024), 0, st, keys, 2u, 2048u, 1u);
+void bitonic_sort_u64(uint64_t* keys, uint32_t npad, hipStream_t st, LaunchLog* log) {
+    launch_logged(log, 0, k_bitonic_local, dim3(npad / 2048), dim3(1024), 0, st, keys, 2u, 2048u, 1u);
     for (uint32_t k = 4096; k <= npad; k <<= 1) {
         for (uint32_t j = k >> 1; j >= 2048; j >>= 1)
-            hipLaunchKernelGGL(k_bitonic_global, dim3(npad / 1024), dim3(1024), 0, st, keys, k, j);
-        hipLaunchKernelGGL(k_bitonic_local, dim3(npad / 2048), dim3(1024), 0, st, keys, k, k, 1024u);
+            launch_logged(log, 0, k_bitonic_global, dim3(npad / 1024), dim3(1024), 0, st, keys, k, j);
+        launch_logged(log, 0, k_bitonic_local, dim3(npad / 2048), dim3(1024), 0, st, keys, k, k, 1024u);
     }
 }
 
@@ -425,7 +443,7 @@ void mesh_bvh_free(MeshBuild& b) {
     b = MeshBuild();
 }
 
-int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std::string& err) {
+int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std::string& err, LaunchLog* log) {
     out = MeshBuild();
     const int nm = s->n_meshes;
     std::vector<int32_t> first((size_t)nm + 1, 0), mat((size_t)nm), rev((size_t)nm);
@@ -537,16 +555,16 @@ int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std
         MB_CHK(hipMemsetAsync(flag, 0, sizeof(uint32_t) * (size_t)n, st));
         MB_CHK(hipMemsetAsync(depth, 0, sizeof(int), st));
         MB_CHK(hipEventRecord(e0, st));
-        hipLaunchKernelGGL(k_centroids, dim3(gb), dim3(kB), 0, st, tris, n, cen, bounds);
-        hipLaunchKernelGGL(k_morton, dim3(gpad), dim3(kB), 0, st, cen, n, npad, bounds, keys);
+        launch_logged(log, 0, k_centroids, dim3(gb), dim3(kB), 0, st, tris, n, cen, bounds);
+        launch_logged(log, 0, k_morton, dim3(gpad), dim3(kB), 0, st, cen, n, npad, bounds, keys);
         // stages k <= 2048 sort each 2048-key block in LDS (one launch); later
         // stages: global passes for strides >= 2048, then the rest in LDS
-        bitonic_sort_u64(keys, (uint32_t)npad, st);
-        hipLaunchKernelGGL(k_gather, dim3(gb), dim3(kB), 0, st, keys, n, tris, gid, out.tris, out.gid);
+        bitonic_sort_u64(keys, (uint32_t)npad, st, log);
+        launch_logged(log, 0, k_gather, dim3(gb), dim3(kB), 0, st, keys, n, tris, gid, out.tris, out.gid);
         if (n > 1)
-            hipLaunchKernelGGL(k_karras, dim3((unsigned)((n - 1 + kB - 1) / kB)), dim3(kB), 0, st, keys, n, cl, cr,
+            launch_logged(log, 0, k_karras, dim3((unsigned)((n - 1 + kB - 1) / kB)), dim3(kB), 0, st, keys, n, cl, cr,
                                par, rfirst);
-        hipLaunchKernelGGL(k_up, dim3(gb), dim3(kB), 0, st, out.tris, n, cl, cr, par, box, tc, sz, ht, flag);
+        launch_logged(log, 0, k_up, dim3(gb), dim3(kB), 0, st, out.tris, n, cl, cr, par, box, tc, sz, ht, flag);
         MB_CHK(hipGetLastError());
 #if PBRT_MESH_WIDE
         {
@@ -567,7 +585,7 @@ int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std
                     mesh_bvh_free(out);
                     return PBRT_E_UNSUPPORTED;
                 }
-                hipLaunchKernelGGL(k_collapse, dim3((e - b + kB - 1) / kB), dim3(kB), 0, st, n, cl, cr, box, tc, ht,
+                launch_logged(log, 0, k_collapse, dim3((e - b + kB - 1) / kB), dim3(kB), 0, st, n, cl, cr, box, tc, ht,
                                    bin_of, par4, b, e, counter, reinterpret_cast<MeshNode4*>(out.nodes));
                 MB_CHK(hipGetLastError());
                 uint32_t next = 0;
@@ -584,7 +602,7 @@ int mesh_bvh_build(const pbrt_scene_desc* s, hipStream_t st, MeshBuild& out, std
         MB_CHK(hipStreamSynchronize(st));
         MB_CHK(dmalloc(&out.nodes, (size_t)kMeshOrders * n_out + kMeshPad));
         MB_CHK(hipMemsetAsync(out.nodes + (size_t)kMeshOrders * n_out, 0, sizeof(MeshNode) * kMeshPad, st));
-        hipLaunchKernelGGL(k_flatten, dim3((unsigned)((2 * n - 1 + kB - 1) / kB)), dim3(kB), 0, st, n, cl, cr, par,
+        launch_logged(log, 0, k_flatten, dim3((unsigned)((2 * n - 1 + kB - 1) / kB)), dim3(kB), 0, st, n, cl, cr, par,
                            rfirst, box, tc, sz, n_out, out.nodes, depth);
 #endif
         MB_CHK(hipEventRecord(e1, st));

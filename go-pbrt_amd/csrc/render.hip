@@ -275,6 +275,10 @@ struct pbrt_gpu_ctx {
     // the queries since the last pbrt_gpu_query_status (allocated by the first)
     pbrtq::BufferList qbufs;
     QueryRec* d_qrec = nullptr;
+    // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
+    // (cleared by render_enqueue) and those outside a frame (LBVH build, queries)
+    LaunchLog log_frame, log_aux;
+    bool in_frame = false;
     std::string err;
     std::chrono::steady_clock::time_point t_start;
 };
@@ -356,6 +360,13 @@ int set_err(pbrt_gpu_ctx* c, int code, const std::string& m) {
         if (e_ != hipSuccess)                                                                        \
             return set_err(ctx, PBRT_E_HIP, std::string(#call ": ") + hipGetErrorString(e_));      \
     } while (0)
+
+// Every launch of a context: the record (launch_log.h), then hipLaunchKernelGGL.
+template <class... P, class... A>
+void launch_k(pbrt_gpu_ctx* c, void (*kern)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
+    const int sid = st == c->stream ? 0 : st == c->stream2 ? 2 : 3;
+    launch_logged(c->in_frame ? &c->log_frame : &c->log_aux, sid, kern, grid, block, lds, st, std::forward<A>(args)...);
+}
 
 template <class T>
 int upload(pbrt_gpu_ctx* c, T** dst, const T* src, size_t n) {
@@ -956,27 +967,27 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
         if (per > 0) {
             HIPCHK(c, hipMemsetAsync(qs.cnt, 0, (size_t)ncnt * 4, c->stream));
             if (nl > 0)
-                hipLaunchKernelGGL(kx ? k_pw_cache<true> : k_pw_cache<false>,
+                launch_k(c, kx ? k_pw_cache<true> : k_pw_cache<false>,
                                    dim3((unsigned)((nr * nl + kWave - 1) / kWave)), dim3(kWave), 0,
                                    c->stream, sc, c->wb, r0, nr, ldc, ldp);
             auto start = kx ? (mb ? k_pw_start<true, true> : k_pw_start<false, true>)
                             : (mb ? k_pw_start<true> : k_pw_start<false>);
-            hipLaunchKernelGGL(start, dim3((unsigned)((nr * per + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
+            launch_k(c, start, dim3((unsigned)((nr * per + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
                                sc, rp, c->wb, sb, r0, nr, ldc, ldp, paths, qs, pkey);
             for (int pass = 0; pass + 1 < rp.max_depth; pass++) {
-                hipLaunchKernelGGL(mesh_only_scene(c) ? k_pw_trace<true> : k_pw_trace<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, 0,
+                launch_k(c, mesh_only_scene(c) ? k_pw_trace<true> : k_pw_trace<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, 0,
                                    n_keys, pkey);
                 if (sort && n_keys > 1) {
-                    hipLaunchKernelGGL(k_pw_scan, dim3(1), dim3(1), 0, c->stream, qs, n_keys);
-                    hipLaunchKernelGGL(k_pw_scatter, dim3(G / 4), dim3(256), 0, c->stream, paths, qs);
+                    launch_k(c, k_pw_scan, dim3(1), dim3(1), 0, c->stream, qs, n_keys);
+                    launch_k(c, k_pw_scatter, dim3(G / 4), dim3(256), 0, c->stream, paths, qs);
                 }
-                hipLaunchKernelGGL(kx ? k_pw_shade<true> : k_pw_shade<false>, dim3(G), dim3(kWave), 0, c->stream, sc,
+                launch_k(c, kx ? k_pw_shade<true> : k_pw_shade<false>, dim3(G), dim3(kWave), 0, c->stream, sc,
                                    rp, c->wb, sb, paths, qs,
                                    sort && n_keys > 1 ? 1 : 0, pkey);
-                hipLaunchKernelGGL(mesh_only_scene(c) ? k_pw_shadow<true> : k_pw_shadow<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, pkey);
+                launch_k(c, mesh_only_scene(c) ? k_pw_shadow<true> : k_pw_shadow<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, pkey);
             }
         }
-        hipLaunchKernelGGL(k_pw_panics, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, sb, r0,
+        launch_k(c, k_pw_panics, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, sb, r0,
                            nr, pkey, c->d_ctr);
     }
     HIPCHK(c, hipGetLastError());
@@ -1265,7 +1276,7 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
     }
     if (scene->n_meshes > 0) {   // triangle meshes: LBVH built on the device (mesh_bvh.hip)
         std::string err;
-        rc = mesh_bvh_build(scene, c->stream, c->mesh, err);
+        rc = mesh_bvh_build(scene, c->stream, c->mesh, err, &c->log_aux);
         if (rc != PBRT_OK) {
             pbrt_gpu_destroy(c);
             return rc;
@@ -1327,7 +1338,7 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
         if (mb) {
             const int64_t blocks = rp.ndims > 0 ? nrec : (nrec + kWave - 1) / kWave;
-            hipLaunchKernelGGL(k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
+            launch_k(c, k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
                                with_slot(sc, 4), rp, c->lay_cam, c->d_jump, c->wb, sb, nb);
         } else {
             const uint32_t* order = nullptr;
@@ -1367,7 +1378,7 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
                 c->h_slot_kw.assign((size_t)nb, (uint8_t)1);
                 c->ci_wps = 3;
             }
-            hipLaunchKernelGGL(k_chain_cam, dim3((unsigned)nb), dim3(kWave), (unsigned)c->lay_cam.total, c->stream,
+            launch_k(c, k_chain_cam, dim3((unsigned)nb), dim3(kWave), (unsigned)c->lay_cam.total, c->stream,
                                with_slot(sc, 2), rp, c->lay_cam, c->d_jump, c->wb, sb, nb, order, ticks);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
@@ -1377,23 +1388,29 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
             const int m = rp.spp - 1, pp = m >= 32 ? 4 : m >= 8 ? 16 : 64;
             auto kern = mb ? (pp == 4 ? k_paths_cam<4, true> : pp == 16 ? k_paths_cam<16, true> : k_paths_cam<64, true>)
                            : (pp == 4 ? k_paths_cam<4, false> : pp == 16 ? k_paths_cam<16, false> : k_paths_cam<64, false>);
-            hipLaunchKernelGGL(kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
+            launch_k(c, kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
                                with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
         if (rp.ndims == 0)
-            hipLaunchKernelGGL(mb ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)nb), dim3(kFilmThreads), 0,
+            launch_k(c, mb ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)nb), dim3(kFilmThreads), 0,
                                c->stream, c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
         else
-            hipLaunchKernelGGL(k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
+            launch_k(c, k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
                                c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
-        hipLaunchKernelGGL(k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, sb, nb,
+        launch_k(c, k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, sb, nb,
                            c->d_panics, c->d_ctr);
     }
     return PBRT_OK;
 }
 
 int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_device) {
+    c->log_frame.clear();
+    struct InFrame {   // the launches until this function returns are the frame's
+        pbrt_gpu_ctx* c;
+        ~InFrame() { c->in_frame = false; }
+    } in_frame{c};
+    c->in_frame = true;
     HIPCHK(c, hipSetDevice(c->device));
     c->t_start = std::chrono::steady_clock::now();
     int rc = prepare(c, rd);
@@ -1441,22 +1458,22 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                                                                                      : paths_group_lds<4>(sl * per);
                     // ordered: whole slots, ceil(ppt / pp) workgroups each (pp need not divide ppt)
                     const int64_t groups = ord ? n * ((c->wb.ppt + pp - 1) / pp) : (n * c->wb.ppt + pp - 1) / pp;
-                    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(kWave),
+                    launch_k(c, kern, dim3((unsigned)groups), dim3(kWave),
                                        (unsigned)lds, st, with_slot(sc, 3), rp, c->wb, sb, n * c->wb.ppt,
                                        c->d_ctr, sl, ord);
                 };
                 c->ov_done = 0;
                 if (c->use_dl) {
-                    hipLaunchKernelGGL(kx ? k_wf_primary<true> : k_wf_primary<false>, dim3((unsigned)((nb * c->wb.ppt + kWave - 1) / kWave)),
+                    launch_k(c, kx ? k_wf_primary<true> : k_wf_primary<false>, dim3((unsigned)((nb * c->wb.ppt + kWave - 1) / kWave)),
                                        dim3(kWave), 0, c->stream, with_slot(sc, 1), rp, c->wb, sb, nb);
                     unsigned lds = 0;
                     const ChainLayout lw = ci_layout(c->lay_ci, 1, 1, lds);
-                    hipLaunchKernelGGL(k_dl_setup, dim3((unsigned)nb), dim3(kWave), lds, c->stream, sc, rp, lw,
+                    launch_k(c, k_dl_setup, dim3((unsigned)nb), dim3(kWave), lds, c->stream, sc, rp, lw,
                                        c->d_jump, c->wb, sb, nb);
                 } else if (rp.mode == PBRT_MODE_THROUGHPUT) {
                     // no offset chain: every sample's stream is known up front
                 } else {
-                    hipLaunchKernelGGL(kx ? k_wf_primary<true> : k_wf_primary<false>,
+                    launch_k(c, kx ? k_wf_primary<true> : k_wf_primary<false>,
                                        dim3((unsigned)((nb * c->wb.ppt + kWave - 1) / kWave)),
                                        dim3(kWave), 0, c->stream, with_slot(sc, 1), rp, c->wb, sb, nb);
                     const int kw = ci_waves(c, nb);
@@ -1507,11 +1524,11 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                                 c->cost_cap = npad;
                             }
                             HIPCHK(c, hipMemsetAsync(c->d_cost_keys, 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
-                            hipLaunchKernelGGL(kx ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)nb),
+                            launch_k(c, kx ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)nb),
                                                dim3(kWave), 0, c->stream, with_slot(sc, 0),
                                                rp, c->wb, sb, nb, c->d_cost, c->d_cost_keys);
-                            bitonic_sort_u64(c->d_cost_keys, (uint32_t)npad, c->stream);
-                            hipLaunchKernelGGL(k_order_of_keys, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0,
+                            bitonic_sort_u64(c->d_cost_keys, (uint32_t)npad, c->stream, &c->log_frame);
+                            launch_k(c, k_order_of_keys, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0,
                                                c->stream, c->d_cost_keys, nb, c->d_slot_order);
                             order = c->d_slot_order;
                             c->probed = true;
@@ -1550,7 +1567,7 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                                            : (w == 2   ? (lds_nodes ? k_chain_ci<2> : k_chain_ci<2, 64>)
                                               : w == 4 ? (lds_nodes ? k_chain_ci<4> : k_chain_ci<4, 64>)
                                                        : (lds_nodes ? k_chain_ci<8> : k_chain_ci<8, 64>));
-                            hipLaunchKernelGGL(kern, dim3((unsigned)n), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
+                            launch_k(c, kern, dim3((unsigned)n), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
                                                c->d_jump, c->wb, sb, nb, kWave * w, ring, c->d_ctr, ord, ticks,
                                                ci_stride(c, w), prog);
                         } else {
@@ -1582,7 +1599,7 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                                    : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true> : k_chain_ci<1, 0, false, 0, true>)
                                    : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2> : k_chain_ci<1, 64, false, 2>)
                                          : (lds_nodes ? k_chain_ci<1> : k_chain_ci<1, 64>));
-                            hipLaunchKernelGGL(kern1, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave),
+                            launch_k(c, kern1, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave),
                                                lds, st, with_slot(sc, 2), rp, lw, c->d_jump, c->wb, sb,
                                                nb, kWave / Gc, ring, c->d_ctr, Gc == 1 ? ord : nullptr,
                                                Gc == 1 ? ticks : nullptr, ci_stride(c, 1), prog);
@@ -1664,7 +1681,7 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                         for (int64_t s0 = 0, j = 0; s0 < nb; j++) {
                             const int64_t e0 = j + 1 >= c->knobs.paths_overlap ? nb
                                                                               : s0 + std::max<int64_t>(1, (nb - s0) / 2);
-                            hipLaunchKernelGGL(k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->d_prog, (uint32_t)s0,
+                            launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->d_prog, (uint32_t)s0,
                                                (uint32_t)e0, c->d_ctr);
                             launch_paths(c->d_prog + kProgHead + s0, e0 - s0, c->stream2);
                             s0 = e0;
@@ -1693,7 +1710,7 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                         HIPCHK(c, hipGetLastError());   // the gates below wait for these workgroups
                         auto light = [&]() -> int {
                             HIPCHK(c, hipStreamWaitEvent(c->stream3, c->knobs.gate_hold ? c->ev_p1 : c->ev_split, 0));
-                            hipLaunchKernelGGL(k_gate, dim3(1), dim3(kWave), 0, c->stream3, c->d_prog,
+                            launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream3, c->d_prog,
                                                (uint32_t)heavy, (uint32_t)heavy, c->d_ctr);
                             launch_ci(light_w, nb - heavy, order + heavy, c->stream3, c->d_prog);
                             HIPCHK(c, hipGetLastError());
@@ -1723,24 +1740,24 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                 if (c->use_dl) {
                     const int64_t nrec = nb * c->wb.ppt;
                     if (rp.spp > 1)
-                        hipLaunchKernelGGL(kx ? k_dl_samples<true> : k_dl_samples<false>,
+                        launch_k(c, kx ? k_dl_samples<true> : k_dl_samples<false>,
                                            dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave,
                                                                             (int64_t)c->n_simd * 64)),
                                            dim3(kWave), 0, c->stream, with_slot(sc, 3), rp, c->wb, sb, nrec);
-                    hipLaunchKernelGGL(k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp,
+                    launch_k(c, k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp,
                                        c->wb, sb, nrec, c->d_ctr);
                 } else if (paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0) {
                     // the path wavefront: mesh scenes, and whatever k_paths_ci cannot
                     // take (a tree beyond LDS, more than 64 / P lights)
                     if (rp.mode == PBRT_MODE_THROUGHPUT)
-                        hipLaunchKernelGGL(kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)), dim3(kWave),
+                        launch_k(c, kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)), dim3(kWave),
                                            (unsigned)c->lay.total, c->stream, with_slot(sc, 4), rp, c->lay, c->d_jump,
                                            c->wb, sb, nb);
                     const int rcp = paths_wavefront(c, with_slot(sc, rp.mode == PBRT_MODE_THROUGHPUT ? 5 : 3), sb, nb);
                     if (rcp != PBRT_OK) return rcp;
                 } else if (rp.mode == PBRT_MODE_THROUGHPUT && paths_ci_pixels(c, rp) > 0) {
                     // setup (StartPixel + bounce 1 per pixel), then lane-refill paths
-                    hipLaunchKernelGGL(kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)),
+                    launch_k(c, kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)),
                                        dim3(kWave), (unsigned)c->lay.total, c->stream, with_slot(sc, 4), rp, c->lay,
                                        c->d_jump, c->wb, sb, nb);
                     const int pp = paths_ci_pixels(c, rp);
@@ -1750,7 +1767,7 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                     const int sl = paths_ci_s1d_lds(c, rp, pp) ? 1 : 0;
                     const int lds = pp == 8 ? paths_group_lds<8>(sl * per) : pp == 2 ? paths_group_lds<2>(sl * per)
                                                                                      : paths_group_lds<4>(sl * per);
-                    hipLaunchKernelGGL(kern, dim3((unsigned)((nb * c->wb.ppt + pp - 1) / pp)), dim3(kWave),
+                    launch_k(c, kern, dim3((unsigned)((nb * c->wb.ppt + pp - 1) / pp)), dim3(kWave),
                                        (unsigned)lds, c->stream, with_slot(sc, 5), rp, c->wb, sb, nb * c->wb.ppt,
                                        c->d_ctr, sl, nullptr);
                 }
@@ -1760,9 +1777,9 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                     launch_paths(nullptr, nb, c->stream);
                 }
                 HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
-                hipLaunchKernelGGL(k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
+                launch_k(c, k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
                                    c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
-                hipLaunchKernelGGL(k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb,
+                launch_k(c, k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb,
                                    sb, nb, c->d_panics, c->d_ctr);
 
             }
@@ -1774,14 +1791,14 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
             if (c->min_waves == 2) kern = k_render_exact<2>;
             else if (c->min_waves == 4) kern = k_render_exact<4>;
             else if (c->min_waves == 8) kern = k_render_exact<8>;
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(kWave), 0, c->stream, with_slot(sc, 6), rp, c->d_films,
+            launch_k(c, kern, dim3((unsigned)blocks), dim3(kWave), 0, c->stream, with_slot(sc, 6), rp, c->d_films,
                                c->d_s1d, c->d_panics, c->d_ctr);
         }
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     int64_t npx = rp.film_w * rp.film_h;
-    hipLaunchKernelGGL(k_merge_film, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film, rp,
+    launch_k(c, k_merge_film, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film, rp,
                        c->d_films, out, c->d_cancel_seen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev2, c->stream));
@@ -1967,7 +1984,7 @@ static int intersect_batch(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, 
     hipError_t e = hipMemcpyAsync(d_in, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         DevScene sc = dev_scene(c, false);
-        hipLaunchKernelGGL(k_intersect, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
+        launch_k(c, k_intersect, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
                            with_slot(sc, 7),
                            (int64_t)n, d_in, d_o, any);
         e = hipGetLastError();
@@ -2042,7 +2059,7 @@ static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool a
     const dim3 grid((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
     const bool mesh_only = c->host_scene.n_prims == 0;   // as the render path chooses its kMeshOnly kernels
 #define PBRT_QUERY_LAUNCH(A, M) \
-    hipLaunchKernelGGL((k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec)
+    launch_k(c, (k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec)
     if (any) {
         if (mesh_only) PBRT_QUERY_LAUNCH(true, true);
         else PBRT_QUERY_LAUNCH(true, false);
@@ -2076,7 +2093,7 @@ int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d,
     if (n > (int64_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
     if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
     HIPCHK(c, hipSetDevice(c->device));
-    hipLaunchKernelGGL(k_query_camera, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0,
+    launch_k(c, k_query_camera, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0,
                        c->stream, c->d_camera, *d, *rays);
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
@@ -2301,7 +2318,7 @@ extern "C" int pbrt_gpu_probe(int device, int op, const double* in, size_t n, in
     }
     hipError_t e = hipMemcpy(d_in, in, sizeof(double) * n * in_stride, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (int64_t)n,
+        launch_logged(nullptr, 0, k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (int64_t)n,
                            in_stride, d_out, out_stride);
         e = hipGetLastError();
     }
@@ -2390,6 +2407,163 @@ extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
     if (!c) return -PBRT_E_INVALID;
     return c->ov_done;
 }
+
+// ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
+// kernel the library compiles, spelled as its explicit instantiation is
+// (tests/test_kernel_manifest.py compares this table with the sources).
+namespace {
+const KernelName kKernelNames[] = {
+    // k_chain_1.hip
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 2, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, true, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, true, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, -1, false, 0, false, false>),
+    // k_chain_n.hip
+    PBRT_KERNEL_NAME(k_chain_ci<2, 0, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<2, 64, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, 0, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, 64, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<8, 0, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<8, 64, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<2, 0, false, 0, true, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, 0, false, 0, true, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<8, 0, false, 0, true, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<2, -1, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, -1, false, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<8, -1, false, 0, false, false>),
+    // k_chain_x.hip
+    PBRT_KERNEL_NAME(k_chain_ci<2, 0, true, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, 0, true, 0, false, false>),
+    // k_chain_g.hip
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 2, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 0, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, true, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, true, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, -1, false, 0, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 0, true, 0, false, true>),
+    // k_paths_m.hip, k_paths_x.hip
+    PBRT_KERNEL_NAME(k_paths_ci<2, false, false>),
+    PBRT_KERNEL_NAME(k_paths_ci<4, false, false>),
+    PBRT_KERNEL_NAME(k_paths_ci<8, false, false>),
+    PBRT_KERNEL_NAME(k_paths_ci<2, true, false>),
+    PBRT_KERNEL_NAME(k_paths_ci<4, true, false>),
+    PBRT_KERNEL_NAME(k_paths_ci<8, true, false>),
+    PBRT_KERNEL_NAME(k_mb_setup<false>),
+    PBRT_KERNEL_NAME(k_paths_ci<4, false, true>),
+    PBRT_KERNEL_NAME(k_paths_ci<8, false, true>),
+    PBRT_KERNEL_NAME(k_paths_ci<4, true, true>),
+    PBRT_KERNEL_NAME(k_paths_ci<8, true, true>),
+    PBRT_KERNEL_NAME(k_mb_setup<true>),
+    // k_chain_c.hip, k_paths_c.hip
+    PBRT_KERNEL_NAME(k_chain_cam),
+    PBRT_KERNEL_NAME(k_cam_setup),
+    PBRT_KERNEL_NAME(k_paths_cam<4, false>),
+    PBRT_KERNEL_NAME(k_paths_cam<16, false>),
+    PBRT_KERNEL_NAME(k_paths_cam<64, false>),
+    PBRT_KERNEL_NAME(k_paths_cam<4, true>),
+    PBRT_KERNEL_NAME(k_paths_cam<16, true>),
+    PBRT_KERNEL_NAME(k_paths_cam<64, true>),
+    PBRT_KERNEL_NAME(k_film_cam<false>),
+    PBRT_KERNEL_NAME(k_film_cam<true>),
+    // k_serial.hip
+    PBRT_KERNEL_NAME(k_render_exact<1>),
+    PBRT_KERNEL_NAME(k_render_exact<2>),
+    PBRT_KERNEL_NAME(k_render_exact<4>),
+    PBRT_KERNEL_NAME(k_render_exact<8>),
+    // k_pw.hip
+    PBRT_KERNEL_NAME(k_pw_trace<false>),
+    PBRT_KERNEL_NAME(k_pw_trace<true>),
+    PBRT_KERNEL_NAME(k_pw_shadow<false>),
+    PBRT_KERNEL_NAME(k_pw_shadow<true>),
+    PBRT_KERNEL_NAME(k_pw_cache<false>),
+    PBRT_KERNEL_NAME(k_pw_cache<true>),
+    PBRT_KERNEL_NAME(k_pw_start<false, false>),
+    PBRT_KERNEL_NAME(k_pw_start<false, true>),
+    PBRT_KERNEL_NAME(k_pw_start<true, false>),
+    PBRT_KERNEL_NAME(k_pw_start<true, true>),
+    PBRT_KERNEL_NAME(k_pw_shade<false>),
+    PBRT_KERNEL_NAME(k_pw_shade<true>),
+    PBRT_KERNEL_NAME(k_pw_scan),
+    PBRT_KERNEL_NAME(k_pw_scatter),
+    PBRT_KERNEL_NAME(k_pw_panics),
+    // k_frame.hip
+    PBRT_KERNEL_NAME(k_film),
+    PBRT_KERNEL_NAME(k_panic_reduce),
+    PBRT_KERNEL_NAME(k_wf_primary<false>),
+    PBRT_KERNEL_NAME(k_wf_primary<true>),
+    PBRT_KERNEL_NAME(k_dl_setup),
+    PBRT_KERNEL_NAME(k_dl_samples<false>),
+    PBRT_KERNEL_NAME(k_dl_samples<true>),
+    PBRT_KERNEL_NAME(k_dl_panics),
+    PBRT_KERNEL_NAME(k_tile_cost<false>),
+    PBRT_KERNEL_NAME(k_tile_cost<true>),
+    PBRT_KERNEL_NAME(k_gate),
+    PBRT_KERNEL_NAME(k_order_of_keys),
+    PBRT_KERNEL_NAME(k_merge_film),
+    PBRT_KERNEL_NAME(k_intersect),
+    // k_group.hip, k_query.hip, this unit
+    PBRT_KERNEL_NAME(k_merge_film_group),
+    PBRT_KERNEL_NAME(k_query_hit<false, false>),
+    PBRT_KERNEL_NAME(k_query_hit<true, false>),
+    PBRT_KERNEL_NAME(k_query_hit<false, true>),
+    PBRT_KERNEL_NAME(k_query_hit<true, true>),
+    PBRT_KERNEL_NAME(k_query_camera),
+    PBRT_KERNEL_NAME(k_probe),
+};
+constexpr size_t kNKernelNames = sizeof(kKernelNames) / sizeof(kKernelNames[0]);
+
+const char* kernel_name_of(const void* fn) {
+    for (size_t i = 0; i < kNKernelNames; i++)
+        if (kKernelNames[i].fn == fn) return kKernelNames[i].name;
+    size_t nm = 0;
+    const KernelName* mk = mesh_bvh_kernel_names(&nm);
+    for (size_t i = 0; i < nm; i++)
+        if (mk[i].fn == fn) return mk[i].name;
+    return "?";
+}
+}  // namespace
+
+extern "C" int pbrt_gpu_kernel_names(const char** out, int n) {
+    size_t nm = 0;
+    const KernelName* mk = mesh_bvh_kernel_names(&nm);
+    int k = 0;
+    for (size_t i = 0; i < kNKernelNames; i++, k++)
+        if (out && k < n) out[k] = kKernelNames[i].name;
+    for (size_t i = 0; i < nm; i++, k++)
+        if (out && k < n) out[k] = mk[i].name;
+    return k;
+}
+
+extern "C" int64_t pbrt_gpu_launch_log(pbrt_gpu_ctx* c, int which, pbrt_launch_rec* out, int64_t n, uint64_t* overflow) {
+    if (!c || (which != PBRT_LAUNCHES_FRAME && which != PBRT_LAUNCHES_OUTSIDE)) return -PBRT_E_INVALID;
+    const LaunchLog& log = which == PBRT_LAUNCHES_FRAME ? c->log_frame : c->log_aux;
+    if (overflow) *overflow = log.overflow;
+    const int64_t m = (int64_t)log.recs.size();
+    if (out && n > 0 && hipSetDevice(c->device) != hipSuccess) return -PBRT_E_HIP;
+    for (int64_t i = 0; out && i < n && i < m; i++) {
+        const LaunchRec& r = log.recs[(size_t)i];
+        pbrt_launch_rec& o = out[i];
+        o.name = kernel_name_of(r.fn);
+        o.fn = r.fn;
+        for (int k = 0; k < 3; k++) {
+            o.grid[k] = r.grid[k];
+            o.block[k] = r.block[k];
+        }
+        o.lds_dynamic = r.lds;
+        hipFuncAttributes fa;
+        o.lds_static = hipFuncGetAttributes(&fa, r.fn) == hipSuccess ? (uint32_t)fa.sharedSizeBytes : 0xFFFFFFFFu;
+        o.stream = r.stream;
+        o.pad0 = 0;
+    }
+    return m;
+}
+
+extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->lds_per_block : -PBRT_E_INVALID; }
 
 extern "C" int pbrt_gpu_schedule_source(pbrt_gpu_ctx* c) {
     if (!c) return -PBRT_E_INVALID;

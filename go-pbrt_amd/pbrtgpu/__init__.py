@@ -66,6 +66,7 @@ def lib():
     L.pbrt_gpu_destroy.restype = None
     abi.declare_group(L)
     abi.declare_query(L)
+    abi.declare_launch_log(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
     L.pbrt_gpu_tile_ticks.argtypes = [C.c_void_p, P(C.c_uint32), i64, P(i64)]
     L.pbrt_gpu_tile_ticks.restype = i64
@@ -172,6 +173,44 @@ def _create_failed(what):
 def build_id():
     """Content hash of the sources the loaded library was built from."""
     return lib().pbrt_gpu_build_id().decode()
+
+
+def kernel_names():
+    """Every kernel name the launch log can produce (pbrt_gpu_kernel_names; needs no GPU)."""
+    n = lib().pbrt_gpu_kernel_names(None, 0)
+    out = (C.c_char_p * n)()
+    lib().pbrt_gpu_kernel_names(out, n)
+    return [s.decode() for s in out]
+
+
+class Launch(tuple):
+    """One record of the launch log: (name, grid, block, lds, stream); grid and block
+    are 3-tuples, lds the dynamic LDS bytes, stream 0 (the context's main stream), 2
+    or 3. lds_static holds the kernel's static LDS bytes."""
+    name = property(lambda s: s[0])
+    grid = property(lambda s: s[1])
+    block = property(lambda s: s[2])
+    lds = property(lambda s: s[3])
+    stream = property(lambda s: s[4])
+    lds_static = 0
+
+
+def _launch_log(ctx, outside):
+    which = abi.PBRT_LAUNCHES_OUTSIDE if outside else abi.PBRT_LAUNCHES_FRAME
+    n = lib().pbrt_gpu_launch_log(ctx, which, None, 0, None)
+    if n < 0:
+        raise PbrtError(-n, "pbrt_gpu_launch_log failed")
+    recs = (abi.LaunchRec * max(n, 1))()
+    over = C.c_uint64(0)
+    n = lib().pbrt_gpu_launch_log(ctx, which, recs, n, C.byref(over))
+    if n < 0:
+        raise PbrtError(-n, "pbrt_gpu_launch_log failed")
+    out = []
+    for r in recs[:n]:
+        rec = Launch((r.name.decode(), tuple(r.grid), tuple(r.block), int(r.lds_dynamic), int(r.stream)))
+        rec.lds_static = int(r.lds_static)
+        out.append(rec)
+    return out, int(over.value)
 
 
 def _d3(v):
@@ -630,6 +669,18 @@ class Renderer:
         (pbrt_gpu_overlap_slots; 0: after the chain stage)."""
         return lib().pbrt_gpu_overlap_slots(self.h)
 
+    def launches(self, outside=False):
+        """The kernel launches of the last frame, in launch order, as (name, grid, block,
+        lds, stream) records (Launch); outside=True: those outside a frame since the
+        context was created (mesh LBVH build, ray queries). This is how to confirm that
+        an environment knob or an option reached the kernel it names."""
+        recs, self.launch_overflow = _launch_log(self.h, outside)
+        return recs
+
+    def lds_per_block(self):
+        """The device's LDS limit per workgroup (bytes)."""
+        return lib().pbrt_gpu_lds_per_block(self.h)
+
     def counters(self):
         """pbrt_gpu_counters of the last render (include/pbrt_diag.h order)."""
         out = np.zeros(128, dtype=np.uint64)
@@ -829,6 +880,11 @@ class RendererGroup:
     def member_schedule_source(self, i):
         """PBRT_SCHED_* of member i's last EXACT frame (pbrt_gpu_schedule_source)."""
         return lib().pbrt_gpu_schedule_source(lib().pbrt_gpu_group_member(self.h, i))
+
+    def member_launches(self, i, outside=False):
+        """Member i's launch log (Renderer.launches). The group's own k_merge_film_group
+        launch belongs to no member context and is not in it."""
+        return _launch_log(lib().pbrt_gpu_group_member(self.h, i), outside)[0]
 
     def cancel(self):
         """Cancel the frame in flight on every member (thread-safe)."""

@@ -283,6 +283,32 @@ def render_desc(spp_x=8, spp_y=8, jitter=False, n_dims=4, integrator=PBRT_INTEGR
     return rd
 
 
+PBRT_LAUNCHES_FRAME, PBRT_LAUNCHES_OUTSIDE = 0, 1
+
+
+class LaunchRec(C.Structure):
+    """pbrt_launch_rec (include/pbrt_diag.h): one kernel launch of a context."""
+    _fields_ = [
+        ("name", C.c_char_p),
+        ("fn", C.c_void_p),
+        ("grid", C.c_uint32 * 3),
+        ("block", C.c_uint32 * 3),
+        ("lds_dynamic", C.c_uint32),
+        ("lds_static", C.c_uint32),
+        ("stream", C.c_int32),
+        ("pad0", C.c_int32),
+    ]
+
+
+def declare_launch_log(L):
+    """ctypes prototypes of the launch log (include/pbrt_diag.h)."""
+    L.pbrt_gpu_launch_log.argtypes = [C.c_void_p, C.c_int, C.POINTER(LaunchRec), C.c_int64, C.POINTER(C.c_uint64)]
+    L.pbrt_gpu_launch_log.restype = C.c_int64
+    L.pbrt_gpu_kernel_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
+    L.pbrt_gpu_lds_per_block.argtypes = [C.c_void_p]
+    L.pbrt_gpu_lds_per_block.restype = C.c_int64
+
+
 PBRT_GROUP_MAX = 8
 
 

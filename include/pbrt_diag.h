@@ -108,6 +108,37 @@ void pbrt_gpu_schedule_cache_clear(void);
  * (PBRT_PATHS_OVERLAP); 0: the path stage ran after the chain stage. */
 int64_t pbrt_gpu_overlap_slots(struct pbrt_gpu_ctx* ctx);
 
+/* The launch log: every kernel a context launches is recorded (host function
+ * pointer, grid, block, dynamic LDS bytes, stream). PBRT_LAUNCHES_FRAME: the
+ * launches of the last frame (cleared when a frame is enqueued; a frame that
+ * pbrt_gpu_synchronize renders again leaves the second rendering's);
+ * PBRT_LAUNCHES_OUTSIDE: those outside a frame since the context was created
+ * (mesh LBVH build, ray queries). A log keeps 4096 records; *overflow counts
+ * the launches beyond. The name is resolved when the log is read: the kernel's
+ * template name with every argument spelled, as its explicit instantiation in
+ * csrc/ does ("k_chain_ci<1, 0, false, 0, false, false>"; static storage).
+ * lds_static: the kernel's static LDS bytes (hipFuncGetAttributes).
+ * stream: 0 the context's main stream, 2, 3 its second and third.
+ * This is how to confirm that an environment knob or an option took effect.
+ * Copies min(n, records) records and returns the record count. */
+enum { PBRT_LAUNCHES_FRAME = 0, PBRT_LAUNCHES_OUTSIDE = 1 };
+typedef struct pbrt_launch_rec {
+    const char* name;
+    const void* fn;
+    uint32_t grid[3];
+    uint32_t block[3];
+    uint32_t lds_dynamic;
+    uint32_t lds_static;
+    int32_t stream;
+    int32_t pad0;
+} pbrt_launch_rec;
+int64_t pbrt_gpu_launch_log(struct pbrt_gpu_ctx* ctx, int which, pbrt_launch_rec* out, int64_t n, uint64_t* overflow);
+/* Every name the log can produce (needs no GPU). Copies min(n, names) pointers
+ * and returns the name count. */
+int pbrt_gpu_kernel_names(const char** out, int n);
+/* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */
+int64_t pbrt_gpu_lds_per_block(struct pbrt_gpu_ctx* ctx);
+
 /* Cold-frame schedule estimate of the last EXACT frame, if that frame ran
  * render.hip's k_tile_cost probe (a fresh context or a new configuration):
  * per slot {chain work (lane-bounces), hit pixels, pixels, cost}. Copies

@@ -37,6 +37,7 @@ import pytest
 
 import oracle_lib as O
 import pbrtgpu as G
+from launch_checks import assert_chain, assert_launched, chain, check_invariants
 from pbrtgpu import abi
 
 pytestmark = pytest.mark.gpu
@@ -89,16 +90,34 @@ def oracle_film(scene_key, rd_items):
     return film, st.paths
 
 
-def check_two_frames(scene_key, lanes_per_wave=0, **rd_kw):
+def check_two_frames(scene_key, lanes_per_wave=0, expect=None, **rd_kw):
+    """expect: the k_chain_ci instantiation the case names (launch_checks.chain), asserted
+    against the two frames' launch logs."""
     ofilm, opaths = oracle_film(scene_key, tuple(sorted(rd_kw.items())))
     assert ofilm.max() > 0
     rd = abi.render_desc(**rd_kw)
+    log = []
     with G.Renderer(SCENES[scene_key](), lanes_per_wave=lanes_per_wave) as r:
         for frame in range(2):
             film, st = r.render(rd)
             assert st.kernel == abi.PBRT_KERNEL_WAVE_CI, (frame, st.kernel)
             assert st.paths_traced == opaths, (frame, st.paths_traced, opaths)
             assert np.array_equal(bits(film), bits(ofilm)), (frame, int((film != ofilm).sum()))
+            log += r.launches()
+            check_invariants(log, r.lds_per_block(), r.launch_overflow)
+    if expect is not None:
+        assert_chain(log, expect, scene_key)
+
+
+def chain_of(scene_key, waves, **kw):
+    """The instantiation a scene's class and PBRT_CI_WAVES select (render.hip launch_ci): the
+    mesh-only walk, the [64]-stack walk beyond 64 nodes, kX; at one wave the register build
+    is ci_eu3_fits' choice unless PBRT_CI_EU sets it."""
+    w = int(waves)
+    depth = {"mesh48x32": -1, "spheres90": 64}.get(scene_key, 0)
+    kx = scene_key == "glass48x32"
+    eu = 0 if (w > 1 or kx or depth < 0) else None
+    return chain(w, depth, kx=kx, eu=kw.pop("eu", eu), multi=kx and w == 1, **kw)
 
 
 @pytest.mark.parametrize("max_depth", [2, 5, 10])
@@ -110,7 +129,8 @@ def test_one_wave(eu, stride, spp, max_depth, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", "1")
     monkeypatch.setenv("PBRT_CI_EU", eu)
     monkeypatch.setenv("PBRT_CI_STRIDE", stride)
-    check_two_frames("readme45x30", spp_x=spp[0], spp_y=spp[1], max_depth=max_depth)
+    check_two_frames("readme45x30", expect=chain(1, eu=0 if eu == "3" else 2), spp_x=spp[0], spp_y=spp[1],
+                     max_depth=max_depth)
 
 
 @pytest.mark.parametrize("n_dims", [1, 2, 3, 4, 5])
@@ -119,7 +139,7 @@ def test_parity_flips(waves, n_dims, monkeypatch):
     """Odd draw counts reset nxt to the head; n_dims also moves the scatter's
     light draws across the stratified / PCG32 boundary."""
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("readme45x30", spp_x=3, spp_y=3, max_depth=5, n_dims=n_dims)
+    check_two_frames("readme45x30", expect=chain_of("readme45x30", waves), spp_x=3, spp_y=3, max_depth=5, n_dims=n_dims)
 
 
 @pytest.mark.parametrize("waves", ["1", "4"])
@@ -127,7 +147,7 @@ def test_long_reach(waves, monkeypatch):
     """Cornell, 20 bounces, no roulette: the longest draw counts of any case here
     (up to 263 draws per pixel; see the module docstring on what that pins)."""
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("cornell32x32", **LONG_REACH)
+    check_two_frames("cornell32x32", expect=chain_of("cornell32x32", waves), **LONG_REACH)
 
 
 @pytest.mark.parametrize("case", [("readme45x30", dict(spp_x=3, spp_y=3)), ("cornell32x32", dict(spp_x=2, spp_y=2))],
@@ -140,32 +160,32 @@ def test_multi_wave(waves, nps, case, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
     if nps != "default":
         monkeypatch.setenv("PBRT_CI_NPS", nps)
-    check_two_frames(case[0], **case[1])
+    check_two_frames(case[0], expect=chain(int(waves)), **case[1])
 
 
 @pytest.mark.parametrize("scene_key", ["mesh48x32", "spheres90"])
 @pytest.mark.parametrize("waves", ["1", "4"])
 def test_mesh_and_stack_walk(waves, scene_key, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames(scene_key, spp_x=2, spp_y=2)
+    check_two_frames(scene_key, expect=chain_of(scene_key, waves), spp_x=2, spp_y=2)
 
 
 def test_windowed_start_pixel():
     """The kSpWin instantiation: 121 spp without jitter on a one-tile image."""
-    check_two_frames("readme16x16", spp_x=11, spp_y=11, jitter=False, max_depth=3)
+    check_two_frames("readme16x16", expect=chain(4, spwin=True), spp_x=11, spp_y=11, jitter=False, max_depth=3)   # 1 tile: 4 waves
 
 
 @pytest.mark.parametrize("lpw", [2, 4])
 def test_several_tiles_per_wave(lpw):
     """kMulti keeps the jump from the pixel's first sample (per-lane group state)."""
-    check_two_frames("readme80x48", lanes_per_wave=lpw, spp_x=2, spp_y=2)
+    check_two_frames("readme80x48", lanes_per_wave=lpw, expect=chain(1, eu=None, multi=True), spp_x=2, spp_y=2)
 
 
 @pytest.mark.parametrize("waves", ["1", "2", "4"])
 def test_kx(waves, monkeypatch):
     """kX: one wave runs the per-lane code (unchanged); 2 and 4 waves carry the state."""
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("glass48x32", spp_x=2, spp_y=2)
+    check_two_frames("glass48x32", expect=chain_of("glass48x32", waves), spp_x=2, spp_y=2)
 
 
 def test_wave_cam():
@@ -182,3 +202,4 @@ def test_wave_cam():
             assert st.kernel == abi.PBRT_KERNEL_WAVE_CAM, (frame, st.kernel)
             assert st.paths_traced == ost.paths, (frame, st.paths_traced, ost.paths)
             assert np.array_equal(bits(film), bits(ofilm)), (frame, int((film != ofilm).sum()))
+            assert_launched(r.launches(), ["k_chain_cam", "k_paths_cam<64, false>", "k_film_cam<false>"], f"frame {frame}")

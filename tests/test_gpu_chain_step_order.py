@@ -27,6 +27,7 @@ import pytest
 
 import oracle_lib as O
 import pbrtgpu as G
+from launch_checks import assert_chain, chain, check_invariants
 from pbrtgpu import abi
 
 pytestmark = pytest.mark.gpu
@@ -96,21 +97,39 @@ def oracle_film(scene_key, rd_items):
     return film, st.paths
 
 
-def check_two_frames(scene_key, lanes_per_wave=0, **rd_kw):
+def check_two_frames(scene_key, lanes_per_wave=0, expect=None, **rd_kw):
+    """expect: the k_chain_ci instantiation the case names (launch_checks.chain), asserted
+    against the two frames' launch logs."""
     ofilm, opaths = oracle_film(scene_key, tuple(sorted(rd_kw.items())))
     assert ofilm.max() > 0
     rd = abi.render_desc(**rd_kw)
+    log = []
     with G.Renderer(SCENES[scene_key](), lanes_per_wave=lanes_per_wave) as r:
         for frame in range(2):
             film, st = r.render(rd)
             assert st.kernel == abi.PBRT_KERNEL_WAVE_CI, (frame, st.kernel)
             assert st.paths_traced == opaths, (frame, st.paths_traced, opaths)
             assert np.array_equal(bits(film), bits(ofilm)), (frame, int((film != ofilm).sum()))
+            log += r.launches()
+            check_invariants(log, r.lds_per_block(), r.launch_overflow)
+    if expect is not None:
+        assert_chain(log, expect, scene_key)
 
 
-def check_case(name, lanes_per_wave=0):
+def chain_of(scene_key, waves, **kw):
+    """The instantiation a scene's class and PBRT_CI_WAVES select (render.hip launch_ci): the
+    mesh-only walk, the [64]-stack walk beyond 64 nodes, kX; at one wave the register build
+    is ci_eu3_fits' choice unless PBRT_CI_EU sets it."""
+    w = int(waves)
+    depth = {"mesh48x32": -1, "spheres90": 64}.get(scene_key, 0)
+    kx = scene_key == "glass48x32"
+    eu = 0 if (w > 1 or kx or depth < 0) else None
+    return chain(w, depth, kx=kx, eu=kw.pop("eu", eu), multi=kx and w == 1, **kw)
+
+
+def check_case(name, lanes_per_wave=0, expect=None):
     scene_key, rd_kw = CASES[name]
-    check_two_frames(scene_key, lanes_per_wave=lanes_per_wave, **rd_kw)
+    check_two_frames(scene_key, lanes_per_wave=lanes_per_wave, expect=expect, **rd_kw)
 
 
 def test_russian_roulette_is_reached():
@@ -127,7 +146,7 @@ def test_one_wave(eu, name, monkeypatch):
     """The one-wave Matte instantiations, at the 3- and the 2-waves/SIMD build."""
     monkeypatch.setenv("PBRT_CI_WAVES", "1")
     monkeypatch.setenv("PBRT_CI_EU", eu)
-    check_case(name)
+    check_case(name, expect=chain(1, eu=0 if eu == "3" else 2))
 
 
 @pytest.mark.parametrize("name", VARIANT_CASES)
@@ -138,14 +157,14 @@ def test_multi_wave(waves, nps, name, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
     if nps != "default":
         monkeypatch.setenv("PBRT_CI_NPS", nps)
-    check_case(name)
+    check_case(name, expect=chain(int(waves)))
 
 
 @pytest.mark.parametrize("name", ["second_scatter80", "cornell_rr1", "cornell_rr025"])
 @pytest.mark.parametrize("lpw", [2, 4])
 def test_several_tiles_per_wave(lpw, name):
     """kMulti: the group's state, and with it the ring of a pending hit, is per lane."""
-    check_case(name, lanes_per_wave=lpw)
+    check_case(name, lanes_per_wave=lpw, expect=chain(1, eu=None, multi=True))
 
 
 @pytest.mark.parametrize("max_depth", [10, 3])
@@ -153,23 +172,23 @@ def test_several_tiles_per_wave(lpw, name):
 def test_kx(waves, max_depth, monkeypatch):
     """kX: a trajectory's RR-branch records are held across the walk."""
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("glass48x32", spp_x=2, spp_y=2, max_depth=max_depth)
+    check_two_frames("glass48x32", expect=chain_of("glass48x32", waves), spp_x=2, spp_y=2, max_depth=max_depth)
 
 
 @pytest.mark.parametrize("max_depth", [10, 3])
 @pytest.mark.parametrize("waves", ["1", "4"])
 def test_mesh(waves, max_depth, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("mesh48x32", spp_x=2, spp_y=2, max_depth=max_depth)
+    check_two_frames("mesh48x32", expect=chain_of("mesh48x32", waves), spp_x=2, spp_y=2, max_depth=max_depth)
 
 
 @pytest.mark.parametrize("max_depth", [6, 2])
 @pytest.mark.parametrize("waves", ["1", "4"])
 def test_stack_walk(waves, max_depth, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("spheres90", spp_x=3, spp_y=3, max_depth=max_depth)
+    check_two_frames("spheres90", expect=chain_of("spheres90", waves), spp_x=3, spp_y=3, max_depth=max_depth)
 
 
 def test_windowed_start_pixel():
     """The kSpWin instantiation: 121 spp without jitter on a one-tile image."""
-    check_two_frames("readme16x16", spp_x=11, spp_y=11, jitter=False, max_depth=3)
+    check_two_frames("readme16x16", expect=chain(4, spwin=True), spp_x=11, spp_y=11, jitter=False, max_depth=3)   # 1 tile: 4 waves

@@ -21,6 +21,7 @@ import pytest
 
 import oracle_lib as O
 import pbrtgpu as G
+from launch_checks import assert_chain, chain, check_invariants
 from pbrtgpu import abi
 
 pytestmark = pytest.mark.gpu
@@ -50,16 +51,23 @@ def oracle_film(scene_key, rd_items):
     return film, st.paths
 
 
-def check_two_frames(scene_key, lanes_per_wave=0, **rd_kw):
+def check_two_frames(scene_key, lanes_per_wave=0, expect=None, **rd_kw):
+    """expect: the k_chain_ci instantiation the case names (launch_checks.chain), asserted
+    against the two frames' launch logs."""
     ofilm, opaths = oracle_film(scene_key, tuple(sorted(rd_kw.items())))
+    assert ofilm.max() > 0
     rd = abi.render_desc(**rd_kw)
+    log = []
     with G.Renderer(SCENES[scene_key](), lanes_per_wave=lanes_per_wave) as r:
         for frame in range(2):
             film, st = r.render(rd)
             assert st.kernel == abi.PBRT_KERNEL_WAVE_CI, (frame, st.kernel)
-            assert st.paths_traced == opaths
+            assert st.paths_traced == opaths, (frame, st.paths_traced, opaths)
             assert np.array_equal(bits(film), bits(ofilm)), (frame, int((film != ofilm).sum()))
-    assert ofilm.max() > 0
+            log += r.launches()
+            check_invariants(log, r.lds_per_block(), r.launch_overflow)
+    if expect is not None:
+        assert_chain(log, expect, scene_key)
 
 
 @pytest.mark.parametrize("spp", [2, 4])
@@ -68,7 +76,7 @@ def test_one_tile_per_wave(eu, spp, monkeypatch):
     """The one-wave instantiations, at the 3- and the 2-waves/SIMD build."""
     monkeypatch.setenv("PBRT_CI_WAVES", "1")
     monkeypatch.setenv("PBRT_CI_EU", eu)
-    check_two_frames("readme45x30", spp_x=spp, spp_y=spp)
+    check_two_frames("readme45x30", expect=chain(1, eu=0 if eu == "3" else 2), spp_x=spp, spp_y=spp)
 
 
 @pytest.mark.parametrize("scene_key", ["readme80x48", "readme45x30"])
@@ -76,7 +84,7 @@ def test_one_tile_per_wave(eu, spp, monkeypatch):
 def test_several_tiles_per_wave(lpw, scene_key):
     """kMulti: groups of one wave in different pixels and phases, of different
     pixel counts, and (80x48: 15 tiles) empty groups in the last wave."""
-    check_two_frames(scene_key, lanes_per_wave=lpw, spp_x=2, spp_y=2)
+    check_two_frames(scene_key, lanes_per_wave=lpw, expect=chain(1, eu=None, multi=True), spp_x=2, spp_y=2)
 
 
 @pytest.mark.parametrize("nps", ["default", "0"])
@@ -86,12 +94,12 @@ def test_multi_wave_tiles(waves, nps, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
     if nps != "default":
         monkeypatch.setenv("PBRT_CI_NPS", nps)
-    check_two_frames("readme45x30", spp_x=4, spp_y=4)
+    check_two_frames("readme45x30", expect=chain(int(waves)), spp_x=4, spp_y=4)
 
 
 def test_windowed_start_pixel():
     """The kSpWin instantiation: 121 spp without jitter on a one-tile image."""
-    check_two_frames("readme16x16", spp_x=11, spp_y=11, jitter=False)
+    check_two_frames("readme16x16", expect=chain(4, spwin=True), spp_x=11, spp_y=11, jitter=False)   # 1 tile: 4 waves
 
 
 @pytest.mark.parametrize("waves", ["1", "2", "4"])
@@ -99,13 +107,13 @@ def test_kx(waves, monkeypatch):
     """kX: per-lane state in the one-wave kernel, scalar in the multi-wave ones
     (6 tiles run 4 waves each by default)."""
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("glass48x32", spp_x=2, spp_y=2)
+    check_two_frames("glass48x32", expect=chain(int(waves), kx=True, multi=waves == "1"), spp_x=2, spp_y=2)
 
 
 @pytest.mark.parametrize("waves", ["1", "4"])
 def test_mesh(waves, monkeypatch):
     monkeypatch.setenv("PBRT_CI_WAVES", waves)
-    check_two_frames("mesh48x32", spp_x=2, spp_y=2)
+    check_two_frames("mesh48x32", expect=chain(int(waves), -1), spp_x=2, spp_y=2)
 
 
 def panic_scene():
