@@ -12,6 +12,8 @@
 //                    tile's RNG-offset chain), k_paths_ci or the path
 //                    wavefront k_pw_* (full paths), k_film (tile films);
 //                    THROUGHPUT mode: k_mb_setup instead of the chain.
+//                    More lights than k_paths_ci's LDS cache holds
+//                    (kMaxCachedLights) run the path wavefront.
 //   camera-start route  (PBRT_KERNEL_WAVE_CAM, opt-in) the wave pipeline for
 //                    renders whose camera ray belongs to the sample (n_dims 0,
 //                    or 1 with a thin lens): k_chain_cam, k_paths_cam,
@@ -657,12 +659,14 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
     // Mirror, smooth Glass and OrenNayar: Path renders run the kX instantiations
     // of the wave pipeline (trajectories and paths over BSDFX, with etaScale):
     // k_chain_ci for LDS-staged trees, then k_paths_ci (P = 4, 8) or the path
-    // wavefront (mesh scenes); rough glass (whose every BSDF sample panics) and
-    // larger trees stay on the serial kernel
+    // wavefront (mesh scenes); rough glass (whose every BSDF sample panics) stays
+    // on the serial kernel, and so do EXACT renders of larger trees: the kX chain
+    // has no [64]-stack instantiation. THROUGHPUT mode has no chain, and its
+    // k_mb_setup<true> and the kX path wavefront walk any tree
     // DirectLighting over these materials runs k_dl_samples<kX> (the recursion per
     // sample; maxDepth <= 64 as the serial kernel), rough glass stays serial
     if (c->non_matte && (c->rough_glass || (dl && rd->max_depth > 64) ||
-                         (!dl && (c->host_scene.n_nodes > kLdsNodes ||
+                         (!dl && ((c->host_scene.n_nodes > kLdsNodes && rd->mode != PBRT_MODE_THROUGHPUT) ||
                                   (!paths_wf_enabled(c) && paths_ci_pixels(c, rp) > 0 && paths_ci_pixels(c, rp) < 4)))))
         return false;
     if (dl) {   // k_dl_*: the camera ray must be per pixel (pFilm stratified; pLens stratified or unused)
@@ -675,7 +679,8 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
         return false;
     }
     const int nl = c->host_scene.n_lights;
-    if (!dl && nl > kMaxCachedLights) return false;
+    // (any light count: beyond the kMaxCachedLights of PixelCache::ld[] paths_ci_pixels answers 0
+    // and the path wavefront runs the paths; its k_pw_cache writes global arrays of n_lights per pixel)
     if (!dl && nl > 0) {
         const pbrt_distribution_desc& d = c->host_dist;
         if (!(d.func_int > 0)) return false;
@@ -736,7 +741,8 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
 // Can the camera-start route (PBRT_KERNEL_WAVE_CAM) replay this render exactly?
 // It takes the renders whose camera ray belongs to the sample: n_dims == 0, or
 // n_dims == 1 with a thin lens (cam_sample.h). Path integrator, Matte scenes on an
-// LDS-staged tree; otherwise wave_eligible's conditions. `why` names the reason
+// LDS-staged tree, any light count (the route has no bounce-1 cache: every light
+// sample is estimated where it is drawn); otherwise wave_eligible's conditions. `why` names the reason
 // of a refusal. L: k_chain_cam's / k_cam_setup's dynamic LDS (the StartPixel
 // staging of n_dims == 1, aliased with the offset ring).
 bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const RenderParams& rp, ChainLayout& L,
@@ -755,7 +761,6 @@ bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const 
     if (c->mesh.n_nodes != 0) return no("triangle meshes");
     if (c->host_scene.n_nodes > kLdsNodes) return no("a tree of more than 64 nodes");
     const int nl = c->host_scene.n_lights;
-    if (nl > kMaxCachedLights) return no("more than 16 lights");
     if (nl > 0) {
         const pbrt_distribution_desc& d = c->host_dist;
         if (!(d.func_int > 0)) return no("a light with pdf 0");
@@ -890,8 +895,9 @@ int paths_ci_pixels(const pbrt_gpu_ctx* c, const RenderParams& rp) {
     bool forced = false;
     if (c->knobs.paths_ci == 0) return 0;
     if (c->knobs.paths_ci > 0) pp = c->knobs.paths_ci, forced = true;
-    auto fits = [&](int p) {
-        return c->host_scene.n_nodes <= kLdsNodes && p * c->host_scene.n_lights <= kWave;
+    auto fits = [&](int p) {   // (kMaxCachedLights: PixelCache::ld[]; a forced P = 2 would admit up to 32 lights)
+        return c->host_scene.n_nodes <= kLdsNodes && p * c->host_scene.n_lights <= kWave &&
+               c->host_scene.n_lights <= kMaxCachedLights;
     };
     if (forced) return fits(pp) ? pp : 0;
     // 8 pixels per wave where their lights fit one wave, else 4; stratified

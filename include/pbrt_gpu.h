@@ -301,7 +301,9 @@ typedef struct pbrt_gpu_opts {
  *             tile's path offsets found by a continuous-issue chain of
  *             speculative trajectories + jump-ahead (k_chain_ci), then the
  *             samples as full paths (k_paths_ci, or the per-bounce path
- *             wavefront k_pw_* for mesh scenes and large trees);
+ *             wavefront k_pw_* for mesh scenes, large trees and more than
+ *             16 lights; up to PBRT_MAX_DIST lights). THROUGHPUT mode takes
+ *             Mirror / smooth Glass / OrenNayar on any tree;
  *  WAVE_DL    DirectLighting (n_dims >= 1): pixel-order StartPixel +
  *             jump-ahead, one lane per sample;
  *  WAVE, WAVEFRONT  (round 1's window and wavefront chains, since replaced)
@@ -310,7 +312,7 @@ typedef struct pbrt_gpu_opts {
  *             sample, not to the pixel: n_dims == 0 (Stratified without sampled
  *             dimensions, pbrt_random_sampler; pinhole or thin lens) or
  *             n_dims == 1 with a thin lens. Path integrator, Matte scenes on
- *             trees of <= 64 nodes, every light pdf > 0. Every trajectory of
+ *             trees of <= 64 nodes, any light count, every light pdf > 0. Every trajectory of
  *             the chain (k_chain_cam) and every path (k_paths_cam) starts at
  *             the camera; with n_dims == 0 the film footprint is per sample
  *             (k_film_cam). Opt-in: AUTO keeps such renders on SERIAL, and
