@@ -111,7 +111,11 @@ __global__ __launch_bounds__(kWave * kW) __attribute__((amdgpu_waves_per_eu(kEu 
 #endif
     static_assert(!kMulti || kW == 1, "several tiles per wave: one-wave workgroups only");
     const int tid = threadIdx.x, lane = tid & (kWave - 1), wv = kW > 1 ? uni(tid / kWave) : 0;
-    stage_nodes(sc);
+    // (the kX stack chains: launched on trees beyond kLdsNodes only, which stage_nodes
+    // leaves alone; said at compile time, the staged walk and its 6 KB of LDS arrays drop
+    // out of the kernel. The Matte stack chains keep the run-time test they were built with)
+    if (kX && kDepth > 0) sc.use_lds_nodes = 0;
+    else stage_nodes(sc);
     const int L = kMulti ? lanes_per_tile : kT, G = kMulti ? kWave / L : 1;
     const int g = kMulti ? lane / L : 0, gl = kMulti ? lane - g * L : tid;
     // workgroup -> tile slot: heaviest-first order from the previous frame

@@ -21,9 +21,13 @@
 // camera draws); no next-pixel speculation, no several tiles per wave, no
 // multi-wave tiles.
 //
+// Trees beyond kLdsNodes are not staged: k_chain_cam_stack is the same loop
+// with the reference's [64] traversal stack, one uint16 column per lane in LDS
+// (8 KB), and without the staged walk's code and LDS arrays.
+//
 // Out of scope (the host refuses them for this route): DirectLighting, per-pixel
 // camera rays (n_dims >= 2, or n_dims = 1 with a pinhole), Mirror / Glass /
-// OrenNayar materials, triangle meshes and trees beyond kLdsNodes.
+// OrenNayar materials and triangle meshes.
 #pragma clang fp contract(off)
 
 #include "render_common.h"
@@ -34,6 +38,15 @@ namespace pbrtk {
 
 #ifndef PBRT_CAM_EU_WAVES
 #define PBRT_CAM_EU_WAVES 3   // k_chain_cam waves/SIMD (build option)
+#endif
+#ifndef PBRT_CAM_STACK_EU_WAVES
+// k_chain_cam_stack waves/SIMD (build option). Without the staged walk and its LDS
+// arrays the kernel has 8.1 KB of static LDS (the stack is 8 KB of it) and fits 168
+// VGPRs without scratch, so with the 4 KB ring 13 workgroups share a CU's 160 KB
+// and the 3-wave build really runs 3 per SIMD. Measured on crowd(60) Matte, 1080p,
+// RandomSampler(64), Path(10): 4.59-4.62 s a frame against 5.62-5.66 s for the 2-wave
+// build (169 VGPRs: 2 per SIMD by registers); profiles/large_trees/
+#define PBRT_CAM_STACK_EU_WAVES 3
 #endif
 
 struct CamGroup {
@@ -49,17 +62,30 @@ struct CamGroup {
     int px, py;      // the current pixel's raster coordinates
 };
 
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_EU_WAVES, 8))) void k_chain_cam(
-    DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base,
-    int64_t nslots_batch, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks) {
+// The chain of one tile on one wave; the kernels below own its static LDS (CAM_CHAIN_LDS)
+// and differ in the traversal stack: kDepth entries per lane, one uint16 column per lane,
+// kWave apart (0: an LDS-staged tree, walked without a stack; 64: the reference's, bvh.go:670).
+// A macro in each kernel, not statics of the template: function statics of a template are laid
+// out differently in LDS, and k_chain_cam keeps the static LDS size it had as a plain kernel.
+#define CAM_CHAIN_LDS(kDepth)                                    \
+    __shared__ uint16_t stack_lds[kDepth > 0 ? kDepth * kWave : 1]; \
+    __shared__ CamGroup gs;                                      \
+    __shared__ uint64_t sh_state;                                \
+    __shared__ uint32_t sh_draws
+template <int kDepth>
+__device__ __forceinline__ void chain_cam(DevScene sc, const RenderParams& rp, const ChainLayout& lay,
+                                          const PcgJump* __restrict__ jump, const WaveBufs& wb, int64_t slot_base,
+                                          int64_t nslots_batch, const uint32_t* __restrict__ order,
+                                          uint32_t* __restrict__ ticks, uint16_t* stack_lds, CamGroup& gs,
+                                          uint64_t& sh_state, uint32_t& sh_draws) {
     extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
     const uint64_t t_begin = wall_clock64();
-    __shared__ uint16_t stack_lds[1];   // an LDS-staged tree is walked without a stack
-    __shared__ CamGroup gs;
-    __shared__ uint64_t sh_state;
-    __shared__ uint32_t sh_draws;
     const int tid = threadIdx.x;
-    stage_nodes(sc);
+    // (kDepth > 0: the host launches the kernel on trees beyond kLdsNodes only, which
+    // stage_nodes leaves alone; said at compile time, the staged walk and its LDS
+    // arrays drop out of the kernel)
+    if (kDepth > 0) sc.use_lds_nodes = 0;
+    else stage_nodes(sc);
     const int64_t bs = order ? (int64_t)order[blockIdx.x] : (int64_t)blockIdx.x;
     if (bs >= nslots_batch) return;
     constexpr uint32_t R = kCiRingBytes / sizeof(RingEnt);   // a power of two
@@ -295,6 +321,20 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_
         const uint64_t t_end = wall_clock64();
         ticks[bs] = (uint32_t)min(t_end - t_begin, (uint64_t)0xFFFFFFFFu);
     }
+}
+
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_EU_WAVES, 8))) void k_chain_cam(
+    DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base,
+    int64_t nslots_batch, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks) {
+    CAM_CHAIN_LDS(0);
+    chain_cam<0>(sc, rp, lay, jump, wb, slot_base, nslots_batch, order, ticks, stack_lds, gs, sh_state, sh_draws);
+}
+
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(PBRT_CAM_STACK_EU_WAVES, 8))) void k_chain_cam_stack(
+    DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base,
+    int64_t nslots_batch, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks) {
+    CAM_CHAIN_LDS(64);
+    chain_cam<64>(sc, rp, lay, jump, wb, slot_base, nslots_batch, order, ticks, stack_lds, gs, sh_state, sh_draws);
 }
 
 }  // namespace pbrtk

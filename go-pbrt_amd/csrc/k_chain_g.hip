@@ -22,5 +22,6 @@ template __global__ void k_chain_ci<1, -1, false, 0, false, true>(DevScene sc, R
 
 // BSDFX (Mirror, Glass, OrenNayar)
 template __global__ void k_chain_ci<1, 0, true, 0, false, true>(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, int lanes_per_tile, int ring_size, Counters* __restrict__ ctr, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks, int cstride, uint32_t* __restrict__ prog);
+template __global__ void k_chain_ci<1, 64, true, 0, false, true>(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, int lanes_per_tile, int ring_size, Counters* __restrict__ ctr, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks, int cstride, uint32_t* __restrict__ prog);
 
 }  // namespace pbrtk

@@ -45,6 +45,10 @@ __global__ __launch_bounds__(kWave) void k_cam_setup(DevScene sc, RenderParams r
     }
 }
 
+// k_paths_cam_stack is k_paths_cam for trees beyond kLdsNodes: the same body
+// with the [64] traversal stack, one uint16 column per lane in LDS (8 KB more
+// than k_paths_cam, whose 2 waves/SIMD on a small tree would not survive them).
+//
 // k_paths_ci's lane refill (render_common.h paths_group) with every path
 // started at the camera: a wave owns P pixel records and their (pixel, sample)
 // work list; a path starts from its sample's RNG state (the chain's wb.memb,
@@ -65,15 +69,20 @@ struct CamNoCache {   // path_step's bounce-1 cache: never read by path_step<2>
     int ld_panic[1];
 };
 
-template <int P, bool kMB>
-__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWaves, 8))) void k_paths_cam(
-    DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr) {
+template <int P, bool kMB, int kDepth>
+__device__ __forceinline__ void paths_cam(DevScene sc, const RenderParams& rp, const WaveBufs& wb, int64_t slot_base,
+                                          int64_t nrec, Counters* __restrict__ ctr) {
+    // kDepth 0: an LDS-staged tree, walked without a stack (no stack array)
+    __shared__ uint16_t stack_lds[kDepth > 0 ? kDepth * kStackStride : 1];
     __shared__ CamMeta meta[P + 1];
     __shared__ unsigned long long pkey[P];
     __shared__ Spec lslots[3 * kWave];   // per lane: the radiance sum, then PathStateLds::aux
     __shared__ uint32_t rslots[kWave];
     if (cancel_requested(sc, (blockIdx.x & 63) == 0)) return;   // one wave per workgroup
-    stage_nodes(sc);
+    // (kDepth > 0: launched on trees beyond kLdsNodes only, which stage_nodes leaves alone; said
+    // at compile time, the staged walk and its LDS arrays drop out of the kernel)
+    if (kDepth > 0) sc.use_lds_nodes = 0;
+    else stage_nodes(sc);
     const int lane = threadIdx.x;
     const int n = rp.spp, ndims = rp.ndims;
     const int64_t rec0 = (int64_t)blockIdx.x * P;
@@ -165,7 +174,8 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
             continue;
         }
         if (w >= 0) {
-            if (path_step<2, false>(sc, none, ss, c, ps, rp.max_depth, rp.rr_threshold, nullptr, pnc, bnc)) {
+            if (path_step<2, false>(sc, none, ss, c, ps, rp.max_depth, rp.rr_threshold,
+                                    kDepth > 0 ? stack_lds + lane : nullptr, pnc, bnc)) {
                 const int64_t rec = rec0 + j;
                 double* o = wb.L + sample_index(wb, rec, n, k) * 3;
                 const Spec Lp = *ps.L;
@@ -195,6 +205,18 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
             atomicAdd(&ctr->camera_samples, (unsigned long long)(meta[q].nv - 1));
         }
     }
+}
+
+template <int P, bool kMB>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWaves, 8))) void k_paths_cam(
+    DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr) {
+    paths_cam<P, kMB, 0>(sc, rp, wb, slot_base, nrec, ctr);
+}
+
+template <int P, bool kMB>
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWaves, 8))) void k_paths_cam_stack(
+    DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr) {
+    paths_cam<P, kMB, 64>(sc, rp, wb, slot_base, nrec, ctr);
 }
 
 // The tile film with one filter footprint per sample (n_dims = 0: pFilm is a
@@ -299,6 +321,12 @@ template __global__ void k_paths_cam<64, false>(DevScene sc, RenderParams rp, Wa
 template __global__ void k_paths_cam<4, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
 template __global__ void k_paths_cam<16, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
 template __global__ void k_paths_cam<64, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<4, false>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<16, false>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<64, false>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<4, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<16, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+template __global__ void k_paths_cam_stack<64, true>(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
 template __global__ void k_film_cam<false>(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, double* __restrict__ films, const int* __restrict__ cancel_seen, Counters* __restrict__ ctr);
 template __global__ void k_film_cam<true>(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, double* __restrict__ films, const int* __restrict__ cancel_seen, Counters* __restrict__ ctr);
 

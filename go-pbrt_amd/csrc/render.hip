@@ -17,7 +17,8 @@
 //   camera-start route  (PBRT_KERNEL_WAVE_CAM, opt-in) the wave pipeline for
 //                    renders whose camera ray belongs to the sample (n_dims 0,
 //                    or 1 with a thin lens): k_chain_cam, k_paths_cam,
-//                    k_film_cam; THROUGHPUT mode: k_cam_setup instead of the chain.
+//                    k_film_cam; THROUGHPUT mode: k_cam_setup instead of the chain;
+//                    trees beyond kLdsNodes: k_chain_cam_stack, k_paths_cam_stack.
 //   k_dl_*         DirectLighting: pixel-order StartPixel + jump-ahead, one
 //                    lane per sample.
 //   k_merge_film     Film.MergeFilmTile (film.go:115-132): per output pixel,
@@ -658,16 +659,15 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
     const bool dl = rd->integrator == PBRT_INTEGRATOR_DIRECT_LIGHTING;
     // Mirror, smooth Glass and OrenNayar: Path renders run the kX instantiations
     // of the wave pipeline (trajectories and paths over BSDFX, with etaScale):
-    // k_chain_ci for LDS-staged trees, then k_paths_ci (P = 4, 8) or the path
-    // wavefront (mesh scenes); rough glass (whose every BSDF sample panics) stays
-    // on the serial kernel, and so do EXACT renders of larger trees: the kX chain
-    // has no [64]-stack instantiation. THROUGHPUT mode has no chain, and its
+    // k_chain_ci (kDepth 0 for LDS-staged trees, the [64] stack beyond), then
+    // k_paths_ci (P = 4, 8) or the path wavefront (mesh scenes, trees beyond
+    // kLdsNodes, more than 16 lights); rough glass (whose every BSDF sample
+    // panics) stays on the serial kernel. THROUGHPUT mode has no chain: its
     // k_mb_setup<true> and the kX path wavefront walk any tree
     // DirectLighting over these materials runs k_dl_samples<kX> (the recursion per
     // sample; maxDepth <= 64 as the serial kernel), rough glass stays serial
     if (c->non_matte && (c->rough_glass || (dl && rd->max_depth > 64) ||
-                         (!dl && ((c->host_scene.n_nodes > kLdsNodes && rd->mode != PBRT_MODE_THROUGHPUT) ||
-                                  (!paths_wf_enabled(c) && paths_ci_pixels(c, rp) > 0 && paths_ci_pixels(c, rp) < 4)))))
+                         (!dl && !paths_wf_enabled(c) && paths_ci_pixels(c, rp) > 0 && paths_ci_pixels(c, rp) < 4)))
         return false;
     if (dl) {   // k_dl_*: the camera ray must be per pixel (pFilm stratified; pLens stratified or unused)
         if (rd->n_dims < 1 || (rd->n_dims < 2 && c->host_scene.camera.lens_radius > 0)) return false;
@@ -740,9 +740,10 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
 
 // Can the camera-start route (PBRT_KERNEL_WAVE_CAM) replay this render exactly?
 // It takes the renders whose camera ray belongs to the sample: n_dims == 0, or
-// n_dims == 1 with a thin lens (cam_sample.h). Path integrator, Matte scenes on an
-// LDS-staged tree, any light count (the route has no bounce-1 cache: every light
-// sample is estimated where it is drawn); otherwise wave_eligible's conditions. `why` names the reason
+// n_dims == 1 with a thin lens (cam_sample.h). Path integrator, Matte scenes on a
+// tree of any size (beyond kLdsNodes: the k_*_cam_stack kernels), any light count
+// (the route has no bounce-1 cache: every light sample is estimated where it is
+// drawn); otherwise wave_eligible's conditions. `why` names the reason
 // of a refusal. L: k_chain_cam's / k_cam_setup's dynamic LDS (the StartPixel
 // staging of n_dims == 1, aliased with the offset ring).
 bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const RenderParams& rp, ChainLayout& L,
@@ -759,7 +760,6 @@ bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const 
         return no("n_dims == 1 with a pinhole: the camera ray is the pixel's (the wave_ci route)");
     if (c->non_matte) return no("Mirror / Glass / OrenNayar materials");
     if (c->mesh.n_nodes != 0) return no("triangle meshes");
-    if (c->host_scene.n_nodes > kLdsNodes) return no("a tree of more than 64 nodes");
     const int nl = c->host_scene.n_lights;
     if (nl > 0) {
         const pbrt_distribution_desc& d = c->host_dist;
@@ -1329,6 +1329,10 @@ namespace {
 int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
     const RenderParams& rp = c->rp;
     const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
+    // a tree beyond kLdsNodes is walked with the [64] stack: the k_*_cam_stack kernels. They are
+    // compiled with use_lds_nodes = 0 (no staged walk): select them by this test only, the one
+    // stage_nodes makes, never for a tree the other kernels would stage
+    const bool lds_nodes = c->host_scene.n_nodes <= kLdsNodes;
     c->last_kernel = PBRT_KERNEL_WAVE_CAM;
     c->n_batches = (int)((rp.n_slots + c->wave_batch - 1) / c->wave_batch);
     while ((int)c->bev.size() < 3 * c->n_batches) {
@@ -1384,16 +1388,22 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
                 c->h_slot_kw.assign((size_t)nb, (uint8_t)1);
                 c->ci_wps = 3;
             }
-            launch_k(c, k_chain_cam, dim3((unsigned)nb), dim3(kWave), (unsigned)c->lay_cam.total, c->stream,
-                               with_slot(sc, 2), rp, c->lay_cam, c->d_jump, c->wb, sb, nb, order, ticks);
+            launch_k(c, lds_nodes ? k_chain_cam : k_chain_cam_stack, dim3((unsigned)nb), dim3(kWave),
+                               (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump,
+                               c->wb, sb, nb, order, ticks);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
         if (rp.spp > 1) {
             // pixels per wave: about 256 (pixel, sample) work items, so that the lanes stay
             // filled at a few samples per pixel too
             const int m = rp.spp - 1, pp = m >= 32 ? 4 : m >= 8 ? 16 : 64;
-            auto kern = mb ? (pp == 4 ? k_paths_cam<4, true> : pp == 16 ? k_paths_cam<16, true> : k_paths_cam<64, true>)
-                           : (pp == 4 ? k_paths_cam<4, false> : pp == 16 ? k_paths_cam<16, false> : k_paths_cam<64, false>);
+            auto kern = lds_nodes
+                ? (mb ? (pp == 4 ? k_paths_cam<4, true> : pp == 16 ? k_paths_cam<16, true> : k_paths_cam<64, true>)
+                      : (pp == 4 ? k_paths_cam<4, false> : pp == 16 ? k_paths_cam<16, false> : k_paths_cam<64, false>))
+                : (mb ? (pp == 4 ? k_paths_cam_stack<4, true> : pp == 16 ? k_paths_cam_stack<16, true>
+                                                                         : k_paths_cam_stack<64, true>)
+                      : (pp == 4 ? k_paths_cam_stack<4, false> : pp == 16 ? k_paths_cam_stack<16, false>
+                                                                          : k_paths_cam_stack<64, false>));
             launch_k(c, kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
                                with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
         }
@@ -1564,8 +1574,11 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                             RenderParams rpl = rp;
                             rpl.ci_nps = (!kx && (!split_launch || light_kw) && ci_stride(c, w) == 1) ? c->knobs.ci_nps : 0;
                             const ChainLayout lw = ci_layout(c->lay_ci, w, 1, lds, rpl.ci_nps > 0);
-                            // kX: LDS-staged trees only, at most 4 waves per tile (wave_eligible, ci_waves)
-                            auto kern = kx ? (w == 2 ? k_chain_ci<2, 0, true> : k_chain_ci<4, 0, true>)
+                            // kX: at most 4 waves per tile (ci_waves, ci_heavy_waves). The kX stack chains
+                            // (here and kern1 below) are compiled with use_lds_nodes = 0: select them by
+                            // !lds_nodes only, stage_nodes' own test, never for a tree that is staged
+                            auto kern = kx ? (w == 2 ? (lds_nodes ? k_chain_ci<2, 0, true> : k_chain_ci<2, 64, true>)
+                                                     : (lds_nodes ? k_chain_ci<4, 0, true> : k_chain_ci<4, 64, true>))
                                         : mesh_only ? (w == 2 ? k_chain_ci<2, -1> : w == 4 ? k_chain_ci<4, -1> : k_chain_ci<8, -1>)
                                         : rp.sp_window ? (w == 2 ? k_chain_ci<2, 0, false, 0, true>
                                                           : w == 4 ? k_chain_ci<4, 0, false, 0, true>
@@ -1595,7 +1608,8 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
                             // too (lanes_per_tile = 64): with the scalar state config G measured
                             // 473.5 against 471.5 ms (profiles/chain_sgpr/), so kX has no other
                             // one-wave instantiation
-                            auto kern1 = kx ? k_chain_ci<1, 0, true, 0, false, true>
+                            auto kern1 = kx ? (lds_nodes ? k_chain_ci<1, 0, true, 0, false, true>
+                                                         : k_chain_ci<1, 64, true, 0, false, true>)
                                 : Gc > 1
                                 ? (mesh_only ? k_chain_ci<1, -1, false, 0, false, true>
                                    : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true, true> : k_chain_ci<1, 0, false, 0, true, true>)
@@ -2443,6 +2457,8 @@ const KernelName kKernelNames[] = {
     // k_chain_x.hip
     PBRT_KERNEL_NAME(k_chain_ci<2, 0, true, 0, false, false>),
     PBRT_KERNEL_NAME(k_chain_ci<4, 0, true, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<2, 64, true, 0, false, false>),
+    PBRT_KERNEL_NAME(k_chain_ci<4, 64, true, 0, false, false>),
     // k_chain_g.hip
     PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, false, true>),
     PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, false, true>),
@@ -2452,6 +2468,7 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, true, true>),
     PBRT_KERNEL_NAME(k_chain_ci<1, -1, false, 0, false, true>),
     PBRT_KERNEL_NAME(k_chain_ci<1, 0, true, 0, false, true>),
+    PBRT_KERNEL_NAME(k_chain_ci<1, 64, true, 0, false, true>),
     // k_paths_m.hip, k_paths_x.hip
     PBRT_KERNEL_NAME(k_paths_ci<2, false, false>),
     PBRT_KERNEL_NAME(k_paths_ci<4, false, false>),
@@ -2474,6 +2491,13 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_paths_cam<4, true>),
     PBRT_KERNEL_NAME(k_paths_cam<16, true>),
     PBRT_KERNEL_NAME(k_paths_cam<64, true>),
+    PBRT_KERNEL_NAME(k_chain_cam_stack),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<4, false>),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<16, false>),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<64, false>),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<4, true>),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<16, true>),
+    PBRT_KERNEL_NAME(k_paths_cam_stack<64, true>),
     PBRT_KERNEL_NAME(k_film_cam<false>),
     PBRT_KERNEL_NAME(k_film_cam<true>),
     // k_serial.hip

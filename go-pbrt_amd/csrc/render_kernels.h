@@ -46,6 +46,10 @@ __global__ void k_chain_cam(DevScene sc, RenderParams rp, ChainLayout lay, const
 __global__ void k_cam_setup(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch);
 template <int P, bool kMB>
 __global__ void k_paths_cam(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
+// (trees beyond kLdsNodes: the same kernels with the [64] traversal stack in LDS)
+__global__ void k_chain_cam_stack(DevScene sc, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, const uint32_t* __restrict__ order, uint32_t* __restrict__ ticks);
+template <int P, bool kMB>
+__global__ void k_paths_cam_stack(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nrec, Counters* __restrict__ ctr);
 template <bool kMB>
 __global__ void k_film_cam(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nslots_batch, double* __restrict__ films, const int* __restrict__ cancel_seen, Counters* __restrict__ ctr);
 __global__ void k_merge_film(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, const double* __restrict__ films, double* __restrict__ out, const int* __restrict__ cancel_seen);

@@ -296,14 +296,15 @@ typedef struct pbrt_gpu_opts {
  *             (any render; the only one for n_dims < 3 Path renders,
  *             zero-pdf lights, filter radius >= 1.5 and PBRT_FLAG_PANIC_FIDELITY);
  *  WAVE_CI    the wave pipeline (Path integrator, n_dims >= 3, every light
- *             pdf > 0, filter radius < 1.5, no rough glass; Mirror / smooth
- *             Glass / OrenNayar on trees of <= 64 nodes): per-pixel shared bounce 1, the
+ *             pdf > 0, filter radius < 1.5, no rough glass; Matte, Mirror,
+ *             smooth Glass and OrenNayar on a tree of any size): per-pixel shared bounce 1, the
  *             tile's path offsets found by a continuous-issue chain of
- *             speculative trajectories + jump-ahead (k_chain_ci), then the
+ *             speculative trajectories + jump-ahead (k_chain_ci; trees of more
+ *             than 64 nodes: its instantiations with the reference's [64]
+ *             traversal stack), then the
  *             samples as full paths (k_paths_ci, or the per-bounce path
  *             wavefront k_pw_* for mesh scenes, large trees and more than
- *             16 lights; up to PBRT_MAX_DIST lights). THROUGHPUT mode takes
- *             Mirror / smooth Glass / OrenNayar on any tree;
+ *             16 lights; up to PBRT_MAX_DIST lights);
  *  WAVE_DL    DirectLighting (n_dims >= 1): pixel-order StartPixel +
  *             jump-ahead, one lane per sample;
  *  WAVE, WAVEFRONT  (round 1's window and wavefront chains, since replaced)
@@ -312,13 +313,15 @@ typedef struct pbrt_gpu_opts {
  *             sample, not to the pixel: n_dims == 0 (Stratified without sampled
  *             dimensions, pbrt_random_sampler; pinhole or thin lens) or
  *             n_dims == 1 with a thin lens. Path integrator, Matte scenes on
- *             trees of <= 64 nodes, any light count, every light pdf > 0. Every trajectory of
+ *             a tree of any size, any light count, every light pdf > 0. Every trajectory of
  *             the chain (k_chain_cam) and every path (k_paths_cam) starts at
- *             the camera; with n_dims == 0 the film footprint is per sample
+ *             the camera; trees of more than 64 nodes run k_chain_cam_stack and
+ *             k_paths_cam_stack, the same kernels with the [64] traversal stack;
+ *             with n_dims == 0 the film footprint is per sample
  *             (k_film_cam). Opt-in: AUTO keeps such renders on SERIAL, and
  *             anything else requested with WAVE_CAM is PBRT_E_UNSUPPORTED
  *             (DirectLighting, n_dims >= 2, n_dims == 1 with a pinhole,
- *             Mirror / Glass / OrenNayar, meshes, larger trees, panic fidelity).
+ *             Mirror / Glass / OrenNayar, meshes, panic fidelity).
  * THROUGHPUT mode reports WAVE for the wave pipeline (no chain), and WAVE_CAM
  * for a WAVE_CAM request. */
 /* WAVE kernel: always replay StartPixel serially (the path normally taken

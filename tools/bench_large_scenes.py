@@ -1,16 +1,17 @@
-"""Frame time of the wave routes on scenes beyond 16 lights, and on Mirror / Glass /
-OrenNayar scenes beyond 64 BVH nodes in THROUGHPUT mode, timed as bench.py times a
-step: render_async_into a device-resident film + synchronize per frame, warm-up
+"""Frame time of the wave routes on scenes beyond 16 lights and on scenes beyond 64
+BVH nodes (Mirror / Glass / OrenNayar, and the camera-start route), timed as bench.py
+times a step: render_async_into a device-resident film + synchronize per frame, warm-up
 frames first.
 
     python tools/bench_large_scenes.py --workload a --mode throughput   [--runs 3 --warmup 1]
     python tools/bench_large_scenes.py --workload b
     python tools/bench_large_scenes.py --workload c --kernel wave_cam
+    python tools/bench_large_scenes.py --workload d --kernel wave_cam   [--mode throughput]
     PBRT_GPU_LIB=<the parent commit's library> python tools/bench_large_scenes.py --workload b
 
 Workloads, all at 1920x1080 with Path(10):
   a  tests/large_scenes.py crowd(n=60), four materials (121 BVH nodes), Stratified(8,8).
-     THROUGHPUT mode runs the wave pipeline; EXACT mode stays on the serial kernel.
+     Both modes run the wave pipeline (EXACT: the kX chain with the [64] stack).
      At this size the reference panics on it (Ld > 10 on an OrenNayar sphere): the
      frame is the reference's up to the panic and the JSON line carries the panic
      site; a frame that ends at a panic is no yardstick, use a3 for timings.
@@ -18,6 +19,9 @@ Workloads, all at 1920x1080 with Path(10):
   b  the README scene plus 16 point lights (20 lights), Stratified(8,8)
   c  the same scene under pbrt_random_sampler(64): per-sample camera rays
      (kernel wave_cam; auto and serial run the serial kernel)
+  d  crowd(n=60), Matte (121 BVH nodes), under pbrt_random_sampler(64): the
+     camera-start route's stack kernels (kernel wave_cam; auto and serial run the
+     serial kernel)
 Prints one JSON line: the timed frames (host wall clock, ms), each frame's
 kernels_ms / chain_ms / paths_ms from the device events, st.kernel and the
 frame's chain and path kernels from the launch log. PBRT_GPU_LIB selects another
@@ -37,7 +41,7 @@ sys.path.insert(0, os.path.join(REPO, "tests"))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["a", "a3", "b", "c"])
+    ap.add_argument("--workload", required=True, choices=["a", "a3", "b", "c", "d"])
     ap.add_argument("--kernel", default="auto", choices=["auto", "serial", "wave_ci", "wave_cam"])
     ap.add_argument("--mode", default="exact", choices=["exact", "throughput"])
     ap.add_argument("--runs", type=int, default=3)
@@ -64,10 +68,14 @@ def main():
     elif args.workload == "b":
         scene, rd = readme_lights_scene(w, h, extra=16), abi.render_desc(8, 8, max_depth=10, mode=mode)
         what = "README + 16 point lights"
-    else:
+    elif args.workload == "c":
         scene, rd = readme_lights_scene(w, h, extra=16), abi.render_desc(max_depth=10, mode=mode)
         G.lib().pbrt_random_sampler(64, C.byref(rd))
         what = "README + 16 point lights, RandomSampler(64)"
+    else:
+        scene, rd = crowd(w=w, h=h, kinds=("matte",)), abi.render_desc(max_depth=10, mode=mode)
+        G.lib().pbrt_random_sampler(64, C.byref(rd))
+        what = "crowd(60), Matte, RandomSampler(64)"
     dev = torch.device("cuda", 0)
     film = torch.zeros((h, w, 3), dtype=torch.float64, device=dev)
     frames = []
