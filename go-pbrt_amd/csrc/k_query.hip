@@ -1,5 +1,6 @@
 // k_query.hip — device-resident ray queries (pbrt_gpu_intersect[_p]_device,
-// pbrt_gpu_camera_rays_device): k_query_hit, k_query_camera
+// pbrt_gpu_camera_rays_device): k_query_hit, k_query_camera; and the diagnostic
+// k_query_hit_staged (pbrt_diag_intersect[_p]_staged_device)
 #pragma clang fp contract(off)
 
 #include "render_common.h"
@@ -17,8 +18,8 @@ namespace pbrtk {
 // A ray on which the reference panics is written as a miss and recorded:
 // rec->panics counts them, rec->first keeps the smallest (index << 8 | kind).
 template <bool kAny, bool kMeshOnly>
-__global__ __launch_bounds__(kQueryBlock) void k_query_hit(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits,
-                                                          QueryRec* __restrict__ rec) {
+__device__ __forceinline__ void query_hit_lane(const DevScene& sc, int64_t n, const pbrt_ray_soa& rays,
+                                               const pbrt_hit_soa& hits, QueryRec* __restrict__ rec) {
     uint16_t* stack = nullptr;
     if constexpr (!kMeshOnly) {
         __shared__ uint16_t stack_lds[(kQueryBlock / kWave) * 64 * kStackStride];
@@ -58,6 +59,25 @@ __global__ __launch_bounds__(kQueryBlock) void k_query_hit(DevScene sc, int64_t 
     }
 }
 
+template <bool kAny, bool kMeshOnly>
+__global__ __launch_bounds__(kQueryBlock) void k_query_hit(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits,
+                                                          QueryRec* __restrict__ rec) {
+    query_hit_lane<kAny, kMeshOnly>(sc, n, rays, hits, rec);
+}
+
+// Diagnostic (include/pbrt_diag.h): k_query_hit<kAny, false> over a tree the
+// render kernels stage in LDS. stage_nodes first, by every thread of the block
+// (it holds a __syncthreads(), so before the i >= n return), and bvh_walk_analytic
+// takes its use_lds_nodes branches: the leaf-preorder scan, with the context's
+// culling groups if it has any. The host launches it on trees of at most
+// kLdsNodes nodes only (beyond them stage_nodes stages nothing and this is k_query_hit).
+template <bool kAny>
+__global__ __launch_bounds__(kQueryBlock) void k_query_hit_staged(DevScene sc, int64_t n, pbrt_ray_soa rays,
+                                                                 pbrt_hit_soa hits, QueryRec* __restrict__ rec) {
+    stage_nodes(sc);
+    query_hit_lane<kAny, false>(sc, n, rays, hits, rec);
+}
+
 // PerspectiveCamera.GenerateRay (camera.go:192-242) for every pixel of a window,
 // in raster order: camera_ray as the render kernels call it.
 __global__ __launch_bounds__(kQueryBlock) void k_query_camera(const pbrt_camera_desc* __restrict__ cam,
@@ -76,5 +96,7 @@ template __global__ void k_query_hit<false, false>(DevScene sc, int64_t n, pbrt_
 template __global__ void k_query_hit<true, false>(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
 template __global__ void k_query_hit<false, true>(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
 template __global__ void k_query_hit<true, true>(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
+template __global__ void k_query_hit_staged<false>(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
+template __global__ void k_query_hit_staged<true>(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
 
 }  // namespace pbrtk

@@ -2066,8 +2066,12 @@ static int query_rec_ensure(pbrt_gpu_ctx* c) {
     return PBRT_OK;
 }
 
-static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool any, const pbrt_hit_soa& hits) {
+// staged: the diagnostic k_query_hit_staged (pbrt_diag.h), for trees the render kernels stage in LDS
+static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool any, const pbrt_hit_soa& hits,
+                     bool staged = false) {
     if (!c || !rays || !hits.hit) return PBRT_E_INVALID;
+    if (staged && (c->host_scene.n_nodes > kLdsNodes || c->host_scene.n_meshes > 0))
+        return set_err(c, PBRT_E_INVALID, "the staged query takes trees of at most 64 nodes and no mesh");
     if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz)
         return set_err(c, PBRT_E_INVALID, "a ray array is NULL");
     if (n > (size_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
@@ -2080,7 +2084,10 @@ static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool a
     const bool mesh_only = c->host_scene.n_prims == 0;   // as the render path chooses its kMeshOnly kernels
 #define PBRT_QUERY_LAUNCH(A, M) \
     launch_k(c, (k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec)
-    if (any) {
+    if (staged) {
+        if (any) launch_k(c, k_query_hit_staged<true>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec);
+        else launch_k(c, k_query_hit_staged<false>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec);
+    } else if (any) {
         if (mesh_only) PBRT_QUERY_LAUNCH(true, true);
         else PBRT_QUERY_LAUNCH(true, false);
     } else {
@@ -2101,6 +2108,18 @@ int pbrt_gpu_intersect_p_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_
     h.hit = occluded;
     return query_hit(c, rays, n, true, h);
 }
+
+// pbrt_diag.h: the same queries through the LDS-staged walks of the render kernels
+int pbrt_diag_intersect_staged_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, const pbrt_hit_soa* hits) {
+    if (!hits) return PBRT_E_INVALID;
+    return query_hit(c, rays, n, false, *hits, true);
+}
+int pbrt_diag_intersect_p_staged_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, uint8_t* occluded) {
+    pbrt_hit_soa h{};
+    h.hit = occluded;
+    return query_hit(c, rays, n, true, h, true);
+}
+int pbrt_gpu_cull_groups(pbrt_gpu_ctx* c) { return c ? c->n_groups : -PBRT_E_INVALID; }
 
 int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d, const pbrt_ray_soa_out* rays) {
     if (!c || !d || !rays) return PBRT_E_INVALID;
@@ -2542,6 +2561,8 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_query_hit<true, false>),
     PBRT_KERNEL_NAME(k_query_hit<false, true>),
     PBRT_KERNEL_NAME(k_query_hit<true, true>),
+    PBRT_KERNEL_NAME(k_query_hit_staged<false>),
+    PBRT_KERNEL_NAME(k_query_hit_staged<true>),
     PBRT_KERNEL_NAME(k_query_camera),
     PBRT_KERNEL_NAME(k_probe),
 };

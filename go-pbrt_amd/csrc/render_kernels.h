@@ -57,6 +57,8 @@ __global__ void k_merge_film_group(const pbrt_film_desc* __restrict__ film_desc,
 __global__ void k_intersect(DevScene sc, int64_t n, const double* __restrict__ rays, double* __restrict__ out, int any_hit);
 template <bool kAny, bool kMeshOnly>
 __global__ void k_query_hit(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
+template <bool kAny>
+__global__ void k_query_hit_staged(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
 __global__ void k_query_camera(const pbrt_camera_desc* __restrict__ cam, pbrt_camera_rays_desc d, pbrt_ray_soa_out out);
 
 }  // namespace pbrtk

@@ -731,11 +731,14 @@ class Renderer:
         a = np.ascontiguousarray(array).reshape(-1)
         return self.buffer(a.size, a.dtype).upload(a)
 
-    def intersect_device(self, rays, n, hits):
+    def intersect_device(self, rays, n, hits, staged=False):
         """pbrt_gpu_intersect_device: closest hits of rays[0:n] into the buffers of
         hits ({"hit": uint8, and any of t_max, prim (int32), px..nz}). Enqueue only:
         read the results with DeviceBuffer.download() or after query_status().
-        Returns the status (PBRT_E_INVALID while a render is in flight)."""
+        Returns the status (PBRT_E_INVALID while a render is in flight).
+        staged: the diagnostic pbrt_diag_intersect_staged_device, the same query
+        on the LDS-staged walk of the render kernels (a tree of at most 64 nodes,
+        no mesh; PBRT_E_INVALID otherwise)."""
         unknown = set(hits) - set(HIT_DTYPES)
         if unknown or hits.get("hit") is None:
             raise PbrtError(abi.PBRT_E_INVALID, f"hits: 'hit' is required; unknown {sorted(unknown)}")
@@ -743,14 +746,21 @@ class Renderer:
         hb = [(k, hits[k], HIT_DTYPES[k]) for k in HIT_DTYPES if hits.get(k) is not None]
         check_buffers(self, n, rb + hb)
         rs, hs = _soa(abi.RaySoA, rb), _soa(abi.HitSoA, hb)
-        return lib().pbrt_gpu_intersect_device(self.h, C.byref(rs), n, C.byref(hs))
+        entry = lib().pbrt_diag_intersect_staged_device if staged else lib().pbrt_gpu_intersect_device
+        return entry(self.h, C.byref(rs), n, C.byref(hs))
 
-    def intersect_p_device(self, rays, n, occluded):
-        """pbrt_gpu_intersect_p_device: any-hit flags (uint8 buffer) of rays[0:n]."""
+    def intersect_p_device(self, rays, n, occluded, staged=False):
+        """pbrt_gpu_intersect_p_device: any-hit flags (uint8 buffer) of rays[0:n].
+        staged: pbrt_diag_intersect_p_staged_device (see intersect_device)."""
         rb = _ray_bufs(rays)
         check_buffers(self, n, rb + [("occluded", occluded, np.uint8)])
         rs = _soa(abi.RaySoA, rb)
-        return lib().pbrt_gpu_intersect_p_device(self.h, C.byref(rs), n, C.c_void_p(occluded.ptr))
+        entry = lib().pbrt_diag_intersect_p_staged_device if staged else lib().pbrt_gpu_intersect_p_device
+        return entry(self.h, C.byref(rs), n, C.c_void_p(occluded.ptr))
+
+    def cull_groups(self):
+        """Leaf culling groups of the context's LDS-staged tree (pbrt_gpu_cull_groups; 0: none)."""
+        return lib().pbrt_gpu_cull_groups(self.h)
 
     def camera_rays(self, window=None, film_offset=(0.5, 0.5), lens=(0.5, 0.5), time_u=0.0, out=None):
         """pbrt_gpu_camera_rays_device: the camera rays of the pixel window (x0, y0,

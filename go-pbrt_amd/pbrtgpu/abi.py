@@ -377,5 +377,8 @@ def declare_query(L):
     L.pbrt_gpu_buffer_destroy.restype = None
     L.pbrt_gpu_intersect_device.argtypes = [vp, P(RaySoA), sz, P(HitSoA)]
     L.pbrt_gpu_intersect_p_device.argtypes = [vp, P(RaySoA), sz, vp]
+    L.pbrt_diag_intersect_staged_device.argtypes = [vp, P(RaySoA), sz, P(HitSoA)]   # include/pbrt_diag.h
+    L.pbrt_diag_intersect_p_staged_device.argtypes = [vp, P(RaySoA), sz, vp]
+    L.pbrt_gpu_cull_groups.argtypes = [vp]
     L.pbrt_gpu_camera_rays_device.argtypes = [vp, P(CameraRaysDesc), P(RaySoAOut)]
     L.pbrt_gpu_query_status.argtypes = [vp, P(QueryRecord)]

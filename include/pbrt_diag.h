@@ -139,6 +139,23 @@ int pbrt_gpu_kernel_names(const char** out, int n);
 /* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */
 int64_t pbrt_gpu_lds_per_block(struct pbrt_gpu_ctx* ctx);
 
+/* pbrt_gpu_intersect_device / pbrt_gpu_intersect_p_device (pbrt_gpu.h: the same
+ * buffers, record and status) through the LDS-staged walks of the render
+ * kernels: k_query_hit_staged<kAny> stages the tree as they do, so that
+ * bvh_walk_analytic scans the octant's leaf preorder, with the context's
+ * culling groups if it has any (PBRT_CULL_GROUPS, PBRT_CULL_GROUP), where the
+ * public queries walk with the reference's [64] stack. For tests that put
+ * arbitrary rays on those walks. PBRT_E_INVALID for a tree of more than 64
+ * nodes or a scene with a mesh. */
+struct pbrt_ray_soa;
+struct pbrt_hit_soa;
+int pbrt_diag_intersect_staged_device(struct pbrt_gpu_ctx* ctx, const struct pbrt_ray_soa* rays, size_t n,
+                                      const struct pbrt_hit_soa* hits);
+int pbrt_diag_intersect_p_staged_device(struct pbrt_gpu_ctx* ctx, const struct pbrt_ray_soa* rays, size_t n,
+                                        uint8_t* occluded);
+/* Leaf culling groups of the context's LDS-staged tree (0: none, every leaf is tested). */
+int pbrt_gpu_cull_groups(struct pbrt_gpu_ctx* ctx);
+
 /* Cold-frame schedule estimate of the last EXACT frame, if that frame ran
  * render.hip's k_tile_cost probe (a fresh context or a new configuration):
  * per slot {chain work (lane-bounces), hit pixels, pixels, cost}. Copies

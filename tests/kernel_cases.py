@@ -155,10 +155,11 @@ CASES = {
 }
 
 # Ray queries, outside a frame (tests/test_gpu_kernel_coverage.py test_query_kernels): scene -> kernels.
-# query_hit's kMeshOnly is n_prims == 0, as the render path chooses.
+# query_hit's kMeshOnly is n_prims == 0, as the render path chooses. k_query_hit_staged is the diagnostic
+# entry of include/pbrt_diag.h (Renderer.intersect_device(staged=True)): LDS-staged trees without a mesh.
 QUERY_CASES = {
     "query_analytic": ("readme32x32", ("k_query_camera", "k_query_hit<false, false>", "k_query_hit<true, false>",
-                                       "k_intersect")),
+                                       "k_intersect", "k_query_hit_staged<false>", "k_query_hit_staged<true>")),
     "query_mesh": ("mesh48x32", ("k_query_hit<false, true>", "k_query_hit<true, true>")),
 }
 

@@ -109,6 +109,17 @@ def test_query_kernels(name, monkeypatch):
         packed = np.stack([rays[k] for k in G.RAY_KEYS + ("tmax",)], axis=1)
         rc, batch = r.intersect(packed)
         assert rc == 0
+        staged = any(k.startswith("k_query_hit_staged") for k in kernels)
+        if staged:   # the same queries on the LDS-staged walk (include/pbrt_diag.h)
+            shits = {k: r.buffer(n, dt) for k, dt in G.HIT_DTYPES.items()}
+            socc = r.buffer(n, np.uint8)
+            assert r.intersect_device(ph["rays"], n, shits, staged=True) == 0
+            assert r.intersect_p_device(ph["rays"], n, socc, staged=True) == 0
+            assert r.query_status()[0] == 0
+            sgot = np.stack([shits[k].download().astype(np.float64) for k in G.HIT_DTYPES], axis=1)
+            soccluded = socc.download()
+        else:   # a mesh: the staged entry refuses
+            assert r.intersect_p_device(ph["rays"], n, occ, staged=True) == abi.PBRT_E_INVALID
         log = r.launches(outside=True)[before:]
         check_invariants(log, r.lds_per_block(), r.launch_overflow)
     want = O.intersect(scene.desc, packed, closest=True)   # rows of hit, t_max, prim, p, n
@@ -117,6 +128,9 @@ def test_query_kernels(name, monkeypatch):
     assert np.array_equal(bits(got), bits(want)), int((got != want).sum())
     assert np.array_equal(bits(batch), bits(want)), int((batch != want).sum())
     assert np.array_equal(occluded.astype(np.float64), want_any)
+    if staged:
+        assert np.array_equal(bits(sgot), bits(want)), int((sgot != want).sum())
+        assert np.array_equal(soccluded.astype(np.float64), want_any)
     assert_launched(log, set(kernels) | {"k_query_camera", "k_intersect"}, name)
     mesh_only = scene.desc.n_prims == 0
     other = "false" if mesh_only else "true"
