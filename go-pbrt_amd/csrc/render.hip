@@ -169,7 +169,7 @@ struct pbrt_gpu_ctx {
     hipEvent_t ev_l2 = nullptr, ev_p1 = nullptr;
     int64_t ov_done = 0;                 // slots whose path stage was launched beside the chains
     uint32_t* d_prog = nullptr;
-    int64_t prog_cap = 0;
+    size_t prog_cap = 0;
     // a frame whose k_gate saw the chains stand still (a dispatcher that serialises
     // kernels across streams) is rendered again without the overlap; two such
     // frames in a row turn the overlap off for the context
@@ -242,7 +242,7 @@ struct pbrt_gpu_ctx {
     uint32_t* d_ticks = nullptr;         // [kTickPlanes][slots]
     std::vector<uint32_t> h_tick_clocks; // diagnostics builds: [start | end] clocks of the last frame
     uint32_t* d_slot_order = nullptr;
-    int64_t ticks_cap = 0;
+    size_t ticks_cap = 0, order_cap = 0;
     std::vector<uint32_t> h_slot_order;
     // path wavefront (k_pw_*, PBRT_PATHS_WF=1): path records, queues, counters,
     // bounce-1 light estimates, per-pixel panic keys (grown on demand)
@@ -251,7 +251,8 @@ struct pbrt_gpu_ctx {
     // cold-frame schedule (k_tile_cost): per-slot features and sort keys
     float* d_cost = nullptr;
     uint64_t* d_cost_keys = nullptr;
-    int64_t cost_cap = 0, cost_n = 0;
+    size_t cost_cap = 0, cost_keys_cap = 0;
+    int64_t cost_n = 0;
     bool probed = false;               // the last EXACT frame ran the cost probe
     uint64_t order_key = 0, ticks_key = 0;
     uint64_t scene_hash = 0;           // content hash of the scene (process-wide schedule cache)
@@ -383,6 +384,7 @@ int ensure(pbrt_gpu_ctx* c, T** buf, size_t* cap, size_t n) {
     if (*cap >= n && *buf) return PBRT_OK;
     if (*buf) (void)hipFree(*buf);
     *buf = nullptr;
+    *cap = 0;
     HIPCHK(c, hipMalloc((void**)buf, sizeof(T) * (n ? n : 1)));
     *cap = n;
     return PBRT_OK;
@@ -813,6 +815,97 @@ ChainLayout ci_layout(const ChainLayout& base, int w, int G, unsigned& lds_bytes
     return l;
 }
 
+// Kernel selectors, one per templated family: plain arguments in, the host function pointer of
+// exactly that instantiation out, nullptr for a combination no unit compiles. They decide nothing;
+// which arguments a frame asks for is its launch function's policy, and a launch site turns
+// nullptr into PBRT_E_HIP before it launches anything. pbrt_diag_kernel_choice reads them, and
+// tests/test_kernel_selectors.py holds each table equal to the compiled instantiations.
+using ChainKernel = decltype(&k_chain_ci<1>);
+struct ChainRow { int w, depth; bool kx; int eu; bool spwin, multi; ChainKernel fn; const char* name; };
+#define CHAIN_ROW(...) {__VA_ARGS__, &k_chain_ci<__VA_ARGS__>, "k_chain_ci<" #__VA_ARGS__ ">"}
+const ChainRow kChainKernels[] = {
+    // one wave per tile, the group's state in scalar registers (k_chain_1.hip)
+    CHAIN_ROW(1, 0, false, 0, false, false),  CHAIN_ROW(1, 0, false, 2, false, false),
+    CHAIN_ROW(1, 64, false, 0, false, false), CHAIN_ROW(1, 64, false, 2, false, false),
+    CHAIN_ROW(1, 0, false, 0, true, false),   CHAIN_ROW(1, 0, false, 2, true, false),
+    CHAIN_ROW(1, -1, false, 0, false, false),
+    // 2, 4 or 8 waves per tile (k_chain_n.hip)
+    CHAIN_ROW(2, 0, false, 0, false, false),  CHAIN_ROW(4, 0, false, 0, false, false),
+    CHAIN_ROW(8, 0, false, 0, false, false),  CHAIN_ROW(2, 64, false, 0, false, false),
+    CHAIN_ROW(4, 64, false, 0, false, false), CHAIN_ROW(8, 64, false, 0, false, false),
+    CHAIN_ROW(2, 0, false, 0, true, false),   CHAIN_ROW(4, 0, false, 0, true, false),
+    CHAIN_ROW(8, 0, false, 0, true, false),   CHAIN_ROW(2, -1, false, 0, false, false),
+    CHAIN_ROW(4, -1, false, 0, false, false), CHAIN_ROW(8, -1, false, 0, false, false),
+    // kX at 2 or 4 waves per tile (k_chain_x.hip)
+    CHAIN_ROW(2, 0, true, 0, false, false),   CHAIN_ROW(4, 0, true, 0, false, false),
+    CHAIN_ROW(2, 64, true, 0, false, false),  CHAIN_ROW(4, 64, true, 0, false, false),
+    // the per-lane code: several tiles per wave, and the one-wave kX chain (k_chain_g.hip)
+    CHAIN_ROW(1, 0, false, 0, false, true),   CHAIN_ROW(1, 0, false, 2, false, true),
+    CHAIN_ROW(1, 64, false, 0, false, true),  CHAIN_ROW(1, 64, false, 2, false, true),
+    CHAIN_ROW(1, 0, false, 0, true, true),    CHAIN_ROW(1, 0, false, 2, true, true),
+    CHAIN_ROW(1, -1, false, 0, false, true),  CHAIN_ROW(1, 0, true, 0, false, true),
+    CHAIN_ROW(1, 64, true, 0, false, true),
+};
+#undef CHAIN_ROW
+ChainKernel chain_kernel(int w, int depth, bool kx, int eu, bool spwin, bool multi) {
+    for (const ChainRow& r : kChainKernels)
+        if (r.w == w && r.depth == depth && r.kx == kx && r.eu == eu && r.spwin == spwin && r.multi == multi)
+            return r.fn;
+    return nullptr;
+}
+
+using PathsCiKernel = decltype(&k_paths_ci<4>);
+struct PathsCiRow { int P; bool mb, kx; PathsCiKernel fn; const char* name; };
+#define PATHS_CI_ROW(...) {__VA_ARGS__, &k_paths_ci<__VA_ARGS__>, "k_paths_ci<" #__VA_ARGS__ ">"}
+const PathsCiRow kPathsCiKernels[] = {   // (kX: 4 or 8 pixels per wave)
+    PATHS_CI_ROW(2, false, false), PATHS_CI_ROW(4, false, false), PATHS_CI_ROW(8, false, false),
+    PATHS_CI_ROW(2, true, false),  PATHS_CI_ROW(4, true, false),  PATHS_CI_ROW(8, true, false),
+    PATHS_CI_ROW(4, false, true),  PATHS_CI_ROW(8, false, true),
+    PATHS_CI_ROW(4, true, true),   PATHS_CI_ROW(8, true, true),
+};
+#undef PATHS_CI_ROW
+PathsCiKernel paths_ci_kernel(int P, bool mb, bool kx) {
+    for (const PathsCiRow& r : kPathsCiKernels)
+        if (r.P == P && r.mb == mb && r.kx == kx) return r.fn;
+    return nullptr;
+}
+// dynamic LDS of a k_paths_ci<P> workgroup that stages `staged_values` stratified values (-1: no such P)
+int paths_ci_lds(int P, int staged_values) {
+    switch (P) {
+    case 2: return paths_group_lds<2>(staged_values);
+    case 4: return paths_group_lds<4>(staged_values);
+    case 8: return paths_group_lds<8>(staged_values);
+    default: return -1;
+    }
+}
+
+using PathsCamKernel = decltype(&k_paths_cam<4, false>);
+struct PathsCamRow { int P; bool mb, stack; PathsCamKernel fn; const char* name; };
+#define PATHS_CAM_ROWS(P, mb)                                             \
+    {P, mb, false, &k_paths_cam<P, mb>, "k_paths_cam<" #P ", " #mb ">"}, \
+    {P, mb, true, &k_paths_cam_stack<P, mb>, "k_paths_cam_stack<" #P ", " #mb ">"}
+const PathsCamRow kPathsCamKernels[] = {   // stack: the k_paths_cam_stack kernels of trees beyond kLdsNodes
+    PATHS_CAM_ROWS(4, false), PATHS_CAM_ROWS(16, false), PATHS_CAM_ROWS(64, false),
+    PATHS_CAM_ROWS(4, true),  PATHS_CAM_ROWS(16, true),  PATHS_CAM_ROWS(64, true),
+};
+#undef PATHS_CAM_ROWS
+PathsCamKernel paths_cam_kernel(int P, bool mb, bool stack) {
+    for (const PathsCamRow& r : kPathsCamKernels)
+        if (r.P == P && r.mb == mb && r.stack == stack) return r.fn;
+    return nullptr;
+}
+
+using SerialKernel = decltype(&k_render_exact<1>);
+SerialKernel serial_kernel(int min_waves) {   // the amdgpu_waves_per_eu builds of k_render_exact
+    switch (min_waves) {
+    case 1: return k_render_exact<1>;
+    case 2: return k_render_exact<2>;
+    case 4: return k_render_exact<4>;
+    case 8: return k_render_exact<8>;
+    default: return nullptr;
+    }
+}
+
 // Waves per tile of k_chain_ci for a launch of nb tiles. The frame's EXACT
 // time is bounded below by its slowest tile's chain, so when the tiles of a
 // launch cannot keep every wave slot busy (2 waves/SIMD) a tile gets 2 or 4
@@ -845,10 +938,7 @@ bool ci_split_enabled(const pbrt_gpu_ctx* c) { return c->knobs.ci_split; }
 // (`multi`: the several-tiles-per-wave instantiation, whose static LDS differs)
 bool ci_eu3_fits(const pbrt_gpu_ctx* c, unsigned dyn_lds, bool lds_nodes, bool multi = false) {
     hipFuncAttributes fa;
-    const void* f = multi ? (lds_nodes ? reinterpret_cast<const void*>(&k_chain_ci<1, 0, false, 0, false, true>)
-                                       : reinterpret_cast<const void*>(&k_chain_ci<1, 64, false, 0, false, true>))
-                    : lds_nodes ? reinterpret_cast<const void*>(&k_chain_ci<1>)
-                                : reinterpret_cast<const void*>(&k_chain_ci<1, 64>);
+    const void* f = reinterpret_cast<const void*>(chain_kernel(1, lds_nodes ? 0 : 64, false, 0, false, multi));
     size_t stat = 0;
     if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat = fa.sharedSizeBytes;
     const size_t per_wg = stat + dyn_lds;
@@ -942,13 +1032,7 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
     const size_t need = (size_t)(al(cap * (int64_t)sizeof(PwPath)) + 4 * al(cap * 4) + al(ncnt * 4) +
                                  al(chunk * std::max(nl, 1) * (int64_t)sizeof(Spec)) + al(chunk * std::max(nl, 1) * 4) +
                                  al(nrec * 8));
-    if (c->pw_cap < need || !c->d_pw) {
-        if (c->d_pw) (void)hipFree(c->d_pw);
-        c->d_pw = nullptr;
-        c->pw_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_pw, need));
-        c->pw_cap = need;
-    }
+    if (const int rc = ensure(c, &c->d_pw, &c->pw_cap, need)) return rc;
     unsigned char* p = c->d_pw;
     auto take = [&](int64_t bytes) {
         unsigned char* q = p;
@@ -1025,13 +1109,7 @@ int wave_buffers(pbrt_gpu_ctx* c) {
     if (batch < 1) batch = 1;
     if (batch > rp.n_slots) batch = rp.n_slots > 0 ? rp.n_slots : 1;
     const size_t need = (size_t)(batch * per_tile);
-    if (c->wave_cap < need || !c->d_wave) {
-        if (c->d_wave) (void)hipFree(c->d_wave);
-        c->d_wave = nullptr;
-        c->wave_cap = 0;
-        HIPCHK(c, hipMalloc((void**)&c->d_wave, need));
-        c->wave_cap = need;
-    }
+    if (const int rc = ensure(c, &c->d_wave, &c->wave_cap, need)) return rc;
     WaveBufs& wb = c->wb;
     unsigned char* p = c->d_wave;
     auto take = [&](int64_t bytes_per_tile) {
@@ -1319,6 +1397,107 @@ int pbrt_gpu_render_async_into(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, doub
 }
 
 namespace {
+// ---- The frame's stages, in the order render_enqueue runs them. Each is a plain
+// function over the context, the scene view and the batch.
+
+// Is the tree staged in LDS? (stage_nodes' own test.) A tree beyond kLdsNodes is walked with the
+// [64] stack: the k_*_cam_stack kernels and the kDepth = 64 chains. Those are compiled with
+// use_lds_nodes = 0 (no staged walk): select them by this test only, never for a tree the other
+// kernels would stage.
+bool tree_in_lds(const pbrt_gpu_ctx* c) { return c->host_scene.n_nodes <= kLdsNodes; }
+
+// The chain launch's schedule: workgroup b runs slot order[b] (null: launch order) and records its
+// chain time in ticks (null: not recorded). learned: the order comes from measured chain times.
+struct Schedule {
+    const uint32_t* order = nullptr;
+    uint32_t* ticks = nullptr;
+    bool learned = false;
+};
+// One batch of a wave route: the frame's tile slots [sb, sb + nb), and its chain stage's schedule.
+struct Batch {
+    int64_t bi, sb, nb;
+    Schedule sched;
+};
+
+// Three events per batch (c->bev): before the chain, after the chain, after the paths.
+int ensure_batch_events(pbrt_gpu_ctx* c) {
+    c->n_batches = (int)((c->rp.n_slots + c->wave_batch - 1) / c->wave_batch);
+    while ((int)c->bev.size() < 3 * c->n_batches) {
+        hipEvent_t e;
+        HIPCHK(c, hipEventCreate(&e));
+        c->bev.push_back(e);
+    }
+    return PBRT_OK;
+}
+
+// The schedule of a one-batch frame's chain launch (k_chain_ci, k_chain_cam) under `key`: grows
+// the tick and order buffers, takes the context's own measured order for the key or else the
+// process cache's (a fresh context: another context's measured order for this scene; with
+// cache_heavy_k its heavy count too), uploads it, and arms pbrt_gpu_synchronize's tick readback.
+int chain_schedule(pbrt_gpu_ctx* c, uint64_t key, int64_t nb, bool cache_heavy_k, Schedule& s) {
+    int rc;
+    if ((rc = ensure(c, &c->d_ticks, &c->ticks_cap, (size_t)nb * kTickPlanes)) ||
+        (rc = ensure(c, &c->d_slot_order, &c->order_cap, (size_t)nb)))
+        return rc;
+    auto known = [&] { return c->order_key == key && (int64_t)c->h_slot_order.size() == nb; };
+    bool cached = false;
+    SchedEntry e;
+    if (!known() && ci_order_cache(c) && sched_cache_get(c, key, nb, e)) {
+        c->h_slot_order = std::move(e.order);
+        if (cache_heavy_k) c->heavy_k = e.heavy_k;
+        c->order_key = key;
+        cached = true;
+    }
+    if (known()) {
+        c->sched_src = cached ? PBRT_SCHED_CACHED : PBRT_SCHED_LEARNED;
+        HIPCHK(c, hipMemcpyAsync(c->d_slot_order, c->h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
+                                 hipMemcpyHostToDevice, c->stream));
+        s.order = c->d_slot_order;
+        s.learned = true;
+    }
+    s.ticks = c->d_ticks;
+    c->ticks_pending = true;
+    c->ticks_key = key;
+    c->ticks_n = nb;
+    return PBRT_OK;
+}
+
+// The cold-frame probe: no measured order for this configuration yet, so estimate one from the
+// bounce-1 records (k_tile_cost), sort the keys and write the order to d_slot_order.
+int probe_order(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
+    int64_t npad = 2048;
+    while (npad < b.nb) npad <<= 1;
+    int rc;
+    if ((rc = ensure(c, &c->d_cost, &c->cost_cap, 4 * (size_t)npad)) ||
+        (rc = ensure(c, &c->d_cost_keys, &c->cost_keys_cap, (size_t)npad)))
+        return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_cost_keys, 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
+    launch_k(c, c->non_matte ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)b.nb), dim3(kWave), 0, c->stream,
+             with_slot(sc, 0), c->rp, c->wb, b.sb, b.nb, c->d_cost, c->d_cost_keys);
+    bitonic_sort_u64(c->d_cost_keys, (uint32_t)npad, c->stream, &c->log_frame);
+    launch_k(c, k_order_of_keys, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->d_cost_keys, b.nb,
+             c->d_slot_order);
+    c->probed = true;
+    c->sched_src = PBRT_SCHED_PROBE;
+    c->cost_n = b.nb;
+    return PBRT_OK;
+}
+
+// The end of a batch on both routes: the tile films (the camera route with n_dims == 0:
+// k_film_cam's per-sample footprints; else k_film), then k_panic_reduce.
+void launch_films(pbrt_gpu_ctx* c, const Batch& b) {
+    const RenderParams& rp = c->rp;
+    if (c->use_cam && rp.ndims == 0)
+        launch_k(c, rp.mode == PBRT_MODE_THROUGHPUT ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)b.nb),
+                 dim3(kFilmThreads), 0, c->stream, c->d_film, rp, c->wb, b.sb, b.nb, c->d_films, c->d_cancel_seen,
+                 c->d_ctr);
+    else
+        launch_k(c, k_film, dim3((unsigned)b.nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
+                 c->d_film, rp, c->wb, b.sb, b.nb, c->d_films, c->d_cancel_seen, c->d_ctr);
+    launch_k(c, k_panic_reduce, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, b.sb, b.nb,
+             c->d_panics, c->d_ctr);
+}
+
 // The camera-start route (PBRT_KERNEL_WAVE_CAM), per batch on the one stream:
 // k_chain_cam (EXACT; THROUGHPUT: k_cam_setup), k_paths_cam, then the tile films
 // (k_film_cam's per-sample footprints with n_dims == 0, else k_film) and
@@ -1328,94 +1507,371 @@ namespace {
 // is no bounce-1 record for k_tile_cost to probe from.
 int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
     const RenderParams& rp = c->rp;
-    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
-    // a tree beyond kLdsNodes is walked with the [64] stack: the k_*_cam_stack kernels. They are
-    // compiled with use_lds_nodes = 0 (no staged walk): select them by this test only, the one
-    // stage_nodes makes, never for a tree the other kernels would stage
-    const bool lds_nodes = c->host_scene.n_nodes <= kLdsNodes;
+    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT, stack = !tree_in_lds(c);
     c->last_kernel = PBRT_KERNEL_WAVE_CAM;
-    c->n_batches = (int)((rp.n_slots + c->wave_batch - 1) / c->wave_batch);
-    while ((int)c->bev.size() < 3 * c->n_batches) {
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreate(&e));
-        c->bev.push_back(e);
-    }
+    int rc = ensure_batch_events(c);
+    if (rc != PBRT_OK) return rc;
     c->ov_done = 0;
-    c->probed = false;
+    c->probed = false;   // this route never probes
     for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
-        const int64_t nb = std::min<int64_t>(c->wave_batch, rp.n_slots - sb);
-        const int64_t nrec = nb * c->wb.ppt;
+        Batch b{bi, sb, std::min<int64_t>(c->wave_batch, rp.n_slots - sb)};
+        const int64_t nb = b.nb, nrec = nb * c->wb.ppt;
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
         if (mb) {
             const int64_t blocks = rp.ndims > 0 ? nrec : (nrec + kWave - 1) / kWave;
             launch_k(c, k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
-                               with_slot(sc, 4), rp, c->lay_cam, c->d_jump, c->wb, sb, nb);
+                     with_slot(sc, 4), rp, c->lay_cam, c->d_jump, c->wb, sb, nb);
         } else {
-            const uint32_t* order = nullptr;
-            uint32_t* ticks = nullptr;
             if (c->n_batches == 1 && ci_order_enabled(c)) {
-                if (c->ticks_cap < nb) {
-                    if (c->d_ticks) (void)hipFree(c->d_ticks);
-                    if (c->d_slot_order) (void)hipFree(c->d_slot_order);
-                    c->d_ticks = c->d_slot_order = nullptr;
-                    c->ticks_cap = 0;
-                    HIPCHK(c, hipMalloc((void**)&c->d_ticks, sizeof(uint32_t) * (size_t)nb * kTickPlanes));
-                    HIPCHK(c, hipMalloc((void**)&c->d_slot_order, sizeof(uint32_t) * (size_t)nb));
-                    c->ticks_cap = nb;
-                }
-                const uint64_t key = schedule_key(rp, -1);   // (-1: no k_chain_ci launch has this wave count)
-                bool cached = false;
-                if (!(c->order_key == key && (int64_t)c->h_slot_order.size() == nb) && ci_order_cache(c)) {
-                    SchedEntry e;   // a fresh context: another context's measured order for this scene
-                    if (sched_cache_get(c, key, nb, e)) {
-                        c->h_slot_order = std::move(e.order);
-                        c->order_key = key;
-                        cached = true;
-                    }
-                }
-                if (c->order_key == key && (int64_t)c->h_slot_order.size() == nb) {
-                    c->sched_src = cached ? PBRT_SCHED_CACHED : PBRT_SCHED_LEARNED;
-                    HIPCHK(c, hipMemcpyAsync(c->d_slot_order, c->h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
-                                             hipMemcpyHostToDevice, c->stream));
-                    order = c->d_slot_order;
-                }
+                // key -1: no k_chain_ci launch has this wave count. A cached entry's heavy count is the
+                // chain route's: there is no split here, every slot runs 1 wave at 3 waves/SIMD
+                if ((rc = chain_schedule(c, schedule_key(rp, -1), nb, false, b.sched)) != PBRT_OK) return rc;
                 if (kTickPlanes > 1)  // diagnostics builds read start / end clocks this kernel does not record
                     HIPCHK(c, hipMemsetAsync(c->d_ticks, 0, sizeof(uint32_t) * (size_t)nb * kTickPlanes, c->stream));
-                ticks = c->d_ticks;
-                c->ticks_pending = true;
-                c->ticks_key = key;
-                c->ticks_n = nb;
                 c->h_slot_kw.assign((size_t)nb, (uint8_t)1);
                 c->ci_wps = 3;
             }
-            launch_k(c, lds_nodes ? k_chain_cam : k_chain_cam_stack, dim3((unsigned)nb), dim3(kWave),
-                               (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump,
-                               c->wb, sb, nb, order, ticks);
+            launch_k(c, stack ? k_chain_cam_stack : k_chain_cam, dim3((unsigned)nb), dim3(kWave),
+                     (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump, c->wb, sb, nb,
+                     b.sched.order, b.sched.ticks);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
         if (rp.spp > 1) {
             // pixels per wave: about 256 (pixel, sample) work items, so that the lanes stay
             // filled at a few samples per pixel too
             const int m = rp.spp - 1, pp = m >= 32 ? 4 : m >= 8 ? 16 : 64;
-            auto kern = lds_nodes
-                ? (mb ? (pp == 4 ? k_paths_cam<4, true> : pp == 16 ? k_paths_cam<16, true> : k_paths_cam<64, true>)
-                      : (pp == 4 ? k_paths_cam<4, false> : pp == 16 ? k_paths_cam<16, false> : k_paths_cam<64, false>))
-                : (mb ? (pp == 4 ? k_paths_cam_stack<4, true> : pp == 16 ? k_paths_cam_stack<16, true>
-                                                                         : k_paths_cam_stack<64, true>)
-                      : (pp == 4 ? k_paths_cam_stack<4, false> : pp == 16 ? k_paths_cam_stack<16, false>
-                                                                          : k_paths_cam_stack<64, false>));
+            const PathsCamKernel kern = paths_cam_kernel(pp, mb, stack);
+            if (!kern) return set_err(c, PBRT_E_HIP, "no k_paths_cam instantiation for P = " + std::to_string(pp));
             launch_k(c, kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
-                               with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
+                     with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
-        if (rp.ndims == 0)
-            launch_k(c, mb ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)nb), dim3(kFilmThreads), 0,
-                               c->stream, c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
-        else
-            launch_k(c, k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
-                               c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
-        launch_k(c, k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, sb, nb,
-                           c->d_panics, c->d_ctr);
+        launch_films(c, b);
+    }
+    return PBRT_OK;
+}
+
+// k_wf_primary: bounce 1 of every pixel of the batch.
+void launch_primary(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
+    launch_k(c, c->non_matte ? k_wf_primary<true> : k_wf_primary<false>,
+             dim3((unsigned)((b.nb * c->wb.ppt + kWave - 1) / kWave)), dim3(kWave), 0, c->stream, with_slot(sc, 1),
+             c->rp, c->wb, b.sb, b.nb);
+}
+
+// THROUGHPUT: k_mb_setup (StartPixel + bounce 1 per pixel) instead of the chain.
+void launch_mb_setup(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
+    launch_k(c, c->non_matte ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(b.nb * c->wb.ppt)), dim3(kWave),
+             (unsigned)c->lay.total, c->stream, with_slot(sc, 4), c->rp, c->lay, c->d_jump, c->wb, b.sb, b.nb);
+}
+
+// k_paths_ci (lane-refill paths) over n slots of the batch on stream st; ord: the slots' order,
+// else slots 0 .. n - 1. mb: the THROUGHPUT instantiation (kMB) and its counter slot.
+int launch_paths(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, bool mb, const uint32_t* ord, int64_t n,
+                 hipStream_t st) {
+    const RenderParams& rp = c->rp;
+    const int pp = paths_ci_pixels(c, rp);
+    const int sl = paths_ci_s1d_lds(c, rp, pp) ? 1 : 0;
+    const PathsCiKernel kern = paths_ci_kernel(pp, mb, c->non_matte);
+    const int lds = paths_ci_lds(pp, sl * rp.ndims * rp.spp);
+    if (!kern || lds < 0)
+        return set_err(c, PBRT_E_HIP, "no k_paths_ci instantiation for P = " + std::to_string(pp) +
+                                          (c->non_matte ? ", kX" : ""));
+    // ordered: whole slots, ceil(ppt / pp) workgroups each (pp need not divide ppt)
+    const int64_t groups = ord ? n * ((c->wb.ppt + pp - 1) / pp) : (n * c->wb.ppt + pp - 1) / pp;
+    launch_k(c, kern, dim3((unsigned)groups), dim3(kWave), (unsigned)lds, st, with_slot(sc, mb ? 5 : 3), rp, c->wb,
+             b.sb, n * c->wb.ppt, c->d_ctr, sl, ord);
+    return PBRT_OK;
+}
+
+// One k_chain_ci launch of n workgroups at w waves per tile on stream st, workgroup i on slot
+// ord[i] (identity if null); prog: the completion record of the overlapped path stage, or null.
+// nps_allowed: the caller's leave for next-pixel speculation (k_chain_ci kNps: Matte, stride 1),
+// which only launches of multi-wave tiles use. The heavy launch of a split does without it unless
+// its light tiles are multi-wave too: its two rings' LDS cost the light tiles beside it (1/4 shard
+// of B 132 -> 145 ms; a 1/8 shard, no split: 131.5 -> 127.2 ms).
+// Sets c->ci_wps for a one-wave launch (pbrt_gpu_synchronize's heavy threshold reads it).
+int launch_ci(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int w, int64_t n, const uint32_t* ord,
+              hipStream_t st, uint32_t* prog, bool nps_allowed) {
+    const bool kx = c->non_matte, mesh_only = mesh_only_scene(c), lds_nodes = tree_in_lds(c);
+    RenderParams rpl = c->rp;
+    int Gc = 1, eu = 0;   // tiles per wave; waves/SIMD the build's registers are budgeted for (0: 3)
+    unsigned lds = 0;
+    ChainLayout lw;
+    if (w > 1) {   // one tile per workgroup of w waves; the ring grows with the lanes
+        rpl.ci_nps = (!kx && nps_allowed && ci_stride(c, w) == 1) ? c->knobs.ci_nps : 0;
+        lw = ci_layout(c->lay_ci, w, 1, lds, rpl.ci_nps > 0);
+    } else {
+        Gc = std::min(c->tiles_per_wave, kCiMaxGroups);
+        lw = ci_layout(c->lay_ci, 1, Gc, lds);
+        // Matte analytic scenes: the 3-waves/SIMD build unless the workgroup's LDS (large spp:
+        // StartPixel staging) caps the CU below 3 waves/SIMD, where the 2-wave build (no spills)
+        // is faster (config C: 6.53 vs 7.41 s). kX and mesh chains have no 2-wave build.
+        const bool eu2 = !kx && !mesh_only &&
+                         (c->knobs.ci_eu == 2 || (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes, Gc > 1)));
+        eu = eu2 ? 2 : 0;
+        c->ci_wps = (kx || eu2) ? 2 : 3;
+    }
+    // The instantiation, stated once. Walk: a mesh-only scene has no analytic one (-1), else the
+    // staged tree (0) or the [64] stack (64). rp.sp_window is set for Matte scenes of staged trees
+    // only (prepare). One wave per tile keeps the group's state in scalar registers; several tiles
+    // per wave (opts.lanes_per_wave) run the per-lane kMulti code, and so does the one-wave kX chain
+    // (lanes_per_tile = 64): with the scalar state config G measured 473.5 against 471.5 ms
+    // (profiles/chain_sgpr/), so kX has no other one-wave instantiation. kX runs at most 4 waves
+    // per tile (ci_waves, ci_heavy_waves).
+    const int depth = mesh_only ? -1 : lds_nodes ? 0 : 64;
+    const bool multi = w == 1 && (kx || Gc > 1);
+    const ChainKernel kern = chain_kernel(w, depth, kx, eu, c->rp.sp_window != 0, multi);
+    if (!kern)
+        return set_err(c, PBRT_E_HIP, "no k_chain_ci instantiation for " + std::to_string(w) + " waves, walk " +
+                                          std::to_string(depth) + (kx ? ", kX" : "") + (multi ? ", multi" : ""));
+    const int ring = w * kCiRingBytes / (int)sizeof(RingEnt) / Gc;
+    const bool per_tile = Gc == 1;   // the order and the clocks need one tile per workgroup
+    launch_k(c, kern, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
+             c->d_jump, c->wb, b.sb, b.nb, kWave * w / Gc, ring, c->d_ctr, per_tile ? ord : nullptr,
+             per_tile ? b.sched.ticks : nullptr, ci_stride(c, w), prog);
+    return PBRT_OK;
+}
+
+// The heavy/light split of a k_chain_ci stage: the `heavy` slots at the front of the order run
+// heavy_w waves each in a launch of their own, the rest light_w (0: one launch at kw).
+struct Split {
+    int64_t heavy;
+    int heavy_w, light_w;
+    bool light_kw;   // the light tiles are multi-wave too: both launches keep next-pixel speculation
+};
+// the heaviest tiles of the last frame get 4 waves each; they are launched first, on the main
+// stream, and the rest concurrently on another (same-stream launches would serialise)
+// (multi-GPU shards, where kw > 1: the rest then run at 1 wave per tile, the most efficient per
+// lane; PBRT_CI_LIGHT_KW=1: at kw)
+Split ci_split(const pbrt_gpu_ctx* c, int64_t nb, int kw, bool learned, int G, bool kx, bool mesh_only) {
+    Split s{};
+    s.light_kw = kw > 1 && c->knobs.ci_light_kw;
+    s.light_w = s.light_kw ? kw : 1;
+    s.heavy_w = ci_heavy_waves(c);
+    // measured wins at 1/2 and 1/4 shards (nb > n_simd); a loss at 1/8
+    // (1020 tiles: 294 -> 307 ms), so smaller launches never split
+    // one GPU (kw == 1): since the Matte chain runs 3 waves/SIMD the whole
+    // frame's lane time is below its heaviest tile's chain, so the heaviest
+    // tiles get 4 waves there too (config B: chain 328.5 -> 313.3 ms)
+    // (measured a loss on the mesh chain, D 825 -> 920 ms, and on kX, G 509 -> 517 ms:
+    // one GPU splits only the 3-wave Matte analytic chain)
+    bool split1 = false;
+    if (kw == 1 && G == 1 && !kx && !mesh_only) {
+        unsigned lds1 = 0;
+        (void)ci_layout(c->lay_ci, 1, 1, lds1);
+        split1 = ci_eu3_fits(c, lds1, tree_in_lds(c));
+    }
+    if (learned && G == 1 && (kw > 1 ? nb > c->n_simd : split1) && ci_split_enabled(c))
+        s.heavy = std::min<int64_t>(c->heavy_k, nb);
+    if (ci_heavy_override(c) >= 0 && learned && G == 1)   // tests and experiments force the split
+        s.heavy = std::min<int64_t>(ci_heavy_override(c), nb);
+    // a multi-wave Matte shard that fits the wave slots (1/8 of B: 1020 tiles at 4 waves)
+    // is bound by its heaviest tiles' pixel-serial chains: those at 8 waves, the
+    // rest at kw, next-pixel speculation in both (the N=8 shards' max 121.9 ->
+    // ~107 ms with 32; 4-32 within a few ms; all tiles at 8 waves: 178 ms)
+    if (s.heavy == 0 && ci_heavy_override(c) < 0 && learned && G == 1 && kw > 1 && nb <= c->n_simd && !kx &&
+        !mesh_only && ci_split_enabled(c) && c->knobs.ci_split8 > 0) {
+        s.heavy = std::min<int64_t>(c->knobs.ci_split8, nb / 16);
+        s.light_kw = true;
+        s.light_w = kw;
+        s.heavy_w = 8;
+    }
+    if (s.heavy >= nb) s.heavy = 0;   // nothing left for the light launch: one launch at kw
+    return s;
+}
+
+// PBRT_PATHS_OVERLAP (a learned frame, one tile per workgroup): the completion-driven path stage.
+//  - the heavy launch on the main stream (normal priority);
+//  - the light launch on stream3 (high priority: it wins every slot that frees
+//    while it has workgroups left), behind a k_gate that opens once every heavy
+//    workgroup has started, so it never delays a heavy tile's start;
+//  - the path stage on stream2 (normal priority): chunks of the tiles in their
+//    chains' completion order (k_chain_ci's completion list), each behind a k_gate
+//    that opens when its tiles' chains have ended. The chunks halve (1/2, 1/4, ...
+//    of the tiles; the last 1/2^(K-1)), so most path work is queued while the
+//    chains run and takes the slots they free once no chain workgroup waits.
+// Without a split the one chain launch goes on stream3 (its workgroups win the slots the path
+// chunks also wait for). Progress-driven, not timed (it replaces round 5's timed wait); only the
+// schedule changes, never a result.
+// overlap_arm: stream3 and its events (created on first use), the progress record (layout at
+// kProgHead) grown and reset, and ev_split on the main stream, which every other stream waits for.
+int overlap_arm(pbrt_gpu_ctx* c, int64_t nb) {
+    if (!c->stream3) {
+        int least = 0, greatest = 0;
+        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(c, hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, greatest));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_l2, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ev_p1, hipEventDisableTiming));
+    }
+    const int rc = ensure(c, &c->d_prog, &c->prog_cap, (size_t)(nb + kProgHead));
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipMemsetAsync(c->d_prog, 0, kProgHead * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_prog + kProgHead, 0xFF, sizeof(uint32_t) * (size_t)nb, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_split, c->stream));
+    return PBRT_OK;
+}
+// the path chunks on stream2, each behind its k_gate; ev_p1 when the last is queued
+int launch_path_chunks(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
+    for (int64_t s0 = 0, j = 0; s0 < b.nb; j++) {
+        const int64_t e0 = j + 1 >= c->knobs.paths_overlap ? b.nb : s0 + std::max<int64_t>(1, (b.nb - s0) / 2);
+        launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->d_prog, (uint32_t)s0, (uint32_t)e0, c->d_ctr);
+        const int rc = launch_paths(c, sc, b, false, c->d_prog + kProgHead + s0, e0 - s0, c->stream2);
+        if (rc != PBRT_OK) return rc;
+        s0 = e0;
+    }
+    HIPCHK(c, hipEventRecord(c->ev_p1, c->stream2));
+    return PBRT_OK;
+}
+// the light launch of an overlapped split on stream3, behind its k_gate; ev_l2 when it is queued.
+// PBRT_GATE_HOLD: it waits for the whole path stage (ev_p1) instead of ev_split
+int launch_light_gated(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split& sp) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->knobs.gate_hold ? c->ev_p1 : c->ev_split, 0));
+    launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream3, c->d_prog, (uint32_t)sp.heavy, (uint32_t)sp.heavy,
+             c->d_ctr);
+    const int rc = launch_ci(c, sc, b, sp.light_w, b.nb - sp.heavy, b.sched.order + sp.heavy, c->stream3, c->d_prog, true);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
+    return PBRT_OK;
+}
+
+// The four ways of issuing the chain stage. 1: unsplit, one launch on the main stream (chain_stage).
+// 2: plain split, the heavy launch on the main stream and the light one on stream2.
+int chain_split(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split& sp) {
+    HIPCHK(c, hipEventRecord(c->ev_split, c->stream));
+    int rc = launch_ci(c, sc, b, sp.heavy_w, sp.heavy, b.sched.order, c->stream, nullptr, sp.light_kw);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
+    rc = launch_ci(c, sc, b, sp.light_w, b.nb - sp.heavy, b.sched.order + sp.heavy, c->stream2, nullptr, true);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    return PBRT_OK;
+}
+// 3: overlapped split on streams 0, 3 and 2 (after overlap_arm). PBRT_GATE_HOLD queues the path
+// chunks before the light launch.
+int chain_split_overlap(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split& sp) {
+    int rc = launch_ci(c, sc, b, sp.heavy_w, sp.heavy, b.sched.order, c->stream, c->d_prog, sp.light_kw);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipGetLastError());   // the gates below wait for these workgroups
+    rc = c->knobs.gate_hold ? launch_path_chunks(c, sc, b) : launch_light_gated(c, sc, b, sp);
+    if (rc != PBRT_OK) return rc;
+    rc = c->knobs.gate_hold ? launch_light_gated(c, sc, b, sp) : launch_path_chunks(c, sc, b);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
+    c->ov_done = b.nb;
+    return PBRT_OK;
+}
+// 4: unsplit with overlap: the one chain launch on stream3, the path chunks on stream2 (after overlap_arm).
+int chain_unsplit_overlap(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int kw) {
+    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_split, 0));
+    int rc = launch_ci(c, sc, b, kw, b.nb, b.sched.order, c->stream3, c->d_prog, true);
+    if (rc != PBRT_OK) return rc;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
+    if ((rc = launch_path_chunks(c, sc, b)) != PBRT_OK) return rc;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
+    c->ov_done = b.nb;
+    return PBRT_OK;
+}
+
+// The EXACT Path chain stage of a batch: k_wf_primary, the schedule, the split decision, then the
+// k_chain_ci launches in one of the four ways above.
+int chain_stage(pbrt_gpu_ctx* c, const DevScene& sc, Batch& b) {
+    const RenderParams& rp = c->rp;
+    const int G = c->tiles_per_wave;
+    const bool kx = c->non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
+    const bool mesh_only = mesh_only_scene(c);   // triangle meshes and nothing else: no analytic walk
+    Schedule& s = b.sched;
+    int rc;
+    launch_primary(c, sc, b);
+    const int kw = ci_waves(c, b.nb);
+    if ((kw > 1 || G == 1) && c->n_batches == 1 && ci_order_enabled(c)) {
+        // keyed by the waves per tile; a cached entry brings its heavy count; a frame without a
+        // measured order runs the cold-frame probe
+        if ((rc = chain_schedule(c, schedule_key(rp, kw), b.nb, true, s)) != PBRT_OK) return rc;
+        c->probed = false;
+        if (!s.order && ci_probe_enabled(c) && b.nb <= (int64_t)1 << 24) {
+            if ((rc = probe_order(c, sc, b)) != PBRT_OK) return rc;
+            s.order = c->d_slot_order;
+        }
+    }
+    const Split sp = ci_split(c, b.nb, kw, s.learned, G, kx, mesh_only);
+    c->last_heavy = sp.heavy;
+    if (s.ticks) {   // label every slot with the waves it actually runs at
+        c->h_slot_kw.assign((size_t)b.nb, (uint8_t)(sp.heavy > 0 ? sp.light_w : kw));
+        for (int64_t i = 0; i < sp.heavy; i++) c->h_slot_kw[c->h_slot_order[(size_t)i]] = (uint8_t)sp.heavy_w;
+    }
+    // the completion-driven path stage takes EXACT k_paths_ci (path_stage's last case) and a learned order
+    const bool paths_ci_exact = !(paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0);
+    const bool ov_ok = c->knobs.paths_overlap > 0 && paths_ci_exact && s.learned && !c->ov_retry && c->ov_stalls < 2;
+    const bool overlap = sp.heavy > 0 && ov_ok;
+    // no split: the completion list needs one tile per workgroup
+    const bool overlap1 = sp.heavy == 0 && ov_ok && c->knobs.paths_overlap_all && (kw > 1 || G == 1);
+    if ((overlap || overlap1) && (rc = overlap_arm(c, b.nb)) != PBRT_OK) return rc;
+    if (overlap1) return chain_unsplit_overlap(c, sc, b, kw);
+    if (overlap) return chain_split_overlap(c, sc, b, sp);
+    if (sp.heavy > 0) return chain_split(c, sc, b, sp);
+    return launch_ci(c, sc, b, kw, b.nb, s.order, c->stream, nullptr, true);
+}
+
+// The path stage of a batch, after its chain stage.
+int path_stage(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
+    const RenderParams& rp = c->rp;
+    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
+    if (c->use_dl) {
+        const int64_t nrec = b.nb * c->wb.ppt;
+        if (rp.spp > 1)
+            launch_k(c, c->non_matte ? k_dl_samples<true> : k_dl_samples<false>,
+                     dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave, (int64_t)c->n_simd * 64)),
+                     dim3(kWave), 0, c->stream, with_slot(sc, 3), rp, c->wb, b.sb, nrec);
+        launch_k(c, k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, b.sb, nrec,
+                 c->d_ctr);
+        return PBRT_OK;
+    }
+    if (paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0) {
+        // the path wavefront: mesh scenes, and whatever k_paths_ci cannot
+        // take (a tree beyond LDS, more than 64 / P lights)
+        if (mb) launch_mb_setup(c, sc, b);
+        return paths_wavefront(c, with_slot(sc, mb ? 5 : 3), b.sb, b.nb);
+    }
+    if (mb) {   // setup, then lane-refill paths
+        launch_mb_setup(c, sc, b);
+        return launch_paths(c, sc, b, true, nullptr, b.nb, c->stream);
+    }
+    if (c->ov_done > 0) {   // the completion-driven path stage (stream2) ends the chain stage
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_p1, 0));
+        return PBRT_OK;
+    }
+    return launch_paths(c, sc, b, false, nullptr, b.nb, c->stream);
+}
+
+// The wave pipeline (DirectLighting, THROUGHPUT, EXACT Path on k_chain_ci), per batch: the chain
+// stage, the path stage, the tile films.
+int enqueue_wave(pbrt_gpu_ctx* c, const DevScene& sc) {
+    const RenderParams& rp = c->rp;
+    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
+    c->last_kernel = c->use_dl ? PBRT_KERNEL_WAVE_DL : mb ? PBRT_KERNEL_WAVE : PBRT_KERNEL_WAVE_CI;
+    int rc = ensure_batch_events(c);
+    if (rc != PBRT_OK) return rc;
+    for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
+        Batch b{bi, sb, std::min<int64_t>(c->wave_batch, rp.n_slots - sb)};
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
+        c->ov_done = 0;
+        if (c->use_dl) {
+            launch_primary(c, sc, b);
+            unsigned lds = 0;
+            const ChainLayout lw = ci_layout(c->lay_ci, 1, 1, lds);
+            launch_k(c, k_dl_setup, dim3((unsigned)b.nb), dim3(kWave), lds, c->stream, sc, rp, lw, c->d_jump, c->wb,
+                     sb, b.nb);
+        } else if (!mb) {   // (THROUGHPUT has no offset chain: every sample's stream is known up front)
+            if ((rc = chain_stage(c, sc, b)) != PBRT_OK) return rc;
+        }
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
+        if ((rc = path_stage(c, sc, b)) != PBRT_OK) return rc;
+        HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
+        launch_films(c, b);
     }
     return PBRT_OK;
 }
@@ -1442,384 +1898,24 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (rp.n_slots > 0) {
         DevScene sc = dev_scene(c, rd->integrator == PBRT_INTEGRATOR_PATH);
-        if (c->use_cam) {
-            const int rcc = enqueue_cam(c, sc);
-            if (rcc != PBRT_OK) return rcc;
-        } else if (c->use_spec) {
-            c->last_kernel = c->use_dl ? PBRT_KERNEL_WAVE_DL
-                             : rp.mode == PBRT_MODE_THROUGHPUT ? PBRT_KERNEL_WAVE : PBRT_KERNEL_WAVE_CI;
-            const bool lds_nodes = c->host_scene.n_nodes <= kLdsNodes;
-            const bool kx = c->non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
-            const bool mesh_only = mesh_only_scene(c);   // triangle meshes and nothing else: no analytic walk
-            c->n_batches = (int)((rp.n_slots + c->wave_batch - 1) / c->wave_batch);
-            while ((int)c->bev.size() < 3 * c->n_batches) {
-                hipEvent_t e;
-                HIPCHK(c, hipEventCreate(&e));
-                c->bev.push_back(e);
-            }
-            for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
-                const int64_t nb = std::min<int64_t>(c->wave_batch, rp.n_slots - sb);
-                HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
-                const int G = c->tiles_per_wave;
-                // EXACT k_paths_ci over n slots (ord: the slots' order, else slots 0 .. n - 1)
-                const bool paths_ci_exact = !c->use_dl && rp.mode != PBRT_MODE_THROUGHPUT &&
-                                            !(paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0);
-                auto launch_paths = [&](const uint32_t* ord, int64_t n, hipStream_t st) {
-                    const int pp = paths_ci_pixels(c, rp);
-                    const int per = rp.ndims * rp.spp;
-                    auto kern = kx ? (pp == 8 ? k_paths_ci<8, false, true> : k_paths_ci<4, false, true>)
-                                   : (pp == 8 ? k_paths_ci<8> : pp == 2 ? k_paths_ci<2> : k_paths_ci<4>);
-                    const int sl = paths_ci_s1d_lds(c, rp, pp) ? 1 : 0;
-                    const int lds = pp == 8 ? paths_group_lds<8>(sl * per) : pp == 2 ? paths_group_lds<2>(sl * per)
-                                                                                     : paths_group_lds<4>(sl * per);
-                    // ordered: whole slots, ceil(ppt / pp) workgroups each (pp need not divide ppt)
-                    const int64_t groups = ord ? n * ((c->wb.ppt + pp - 1) / pp) : (n * c->wb.ppt + pp - 1) / pp;
-                    launch_k(c, kern, dim3((unsigned)groups), dim3(kWave),
-                                       (unsigned)lds, st, with_slot(sc, 3), rp, c->wb, sb, n * c->wb.ppt,
-                                       c->d_ctr, sl, ord);
-                };
-                c->ov_done = 0;
-                if (c->use_dl) {
-                    launch_k(c, kx ? k_wf_primary<true> : k_wf_primary<false>, dim3((unsigned)((nb * c->wb.ppt + kWave - 1) / kWave)),
-                                       dim3(kWave), 0, c->stream, with_slot(sc, 1), rp, c->wb, sb, nb);
-                    unsigned lds = 0;
-                    const ChainLayout lw = ci_layout(c->lay_ci, 1, 1, lds);
-                    launch_k(c, k_dl_setup, dim3((unsigned)nb), dim3(kWave), lds, c->stream, sc, rp, lw,
-                                       c->d_jump, c->wb, sb, nb);
-                } else if (rp.mode == PBRT_MODE_THROUGHPUT) {
-                    // no offset chain: every sample's stream is known up front
-                } else {
-                    launch_k(c, kx ? k_wf_primary<true> : k_wf_primary<false>,
-                                       dim3((unsigned)((nb * c->wb.ppt + kWave - 1) / kWave)),
-                                       dim3(kWave), 0, c->stream, with_slot(sc, 1), rp, c->wb, sb, nb);
-                    const int kw = ci_waves(c, nb);
-                    const uint32_t* order = nullptr;
-                    bool learned = false;   // order from the last frame's measured chain times
-                    uint32_t* ticks = nullptr;
-                    if ((kw > 1 || G == 1) && c->n_batches == 1 && ci_order_enabled(c)) {
-                        if (c->ticks_cap < nb) {
-                            if (c->d_ticks) (void)hipFree(c->d_ticks);
-                            if (c->d_slot_order) (void)hipFree(c->d_slot_order);
-                            c->d_ticks = c->d_slot_order = nullptr;
-                            c->ticks_cap = 0;
-                            HIPCHK(c, hipMalloc((void**)&c->d_ticks, sizeof(uint32_t) * (size_t)nb * kTickPlanes));
-                            HIPCHK(c, hipMalloc((void**)&c->d_slot_order, sizeof(uint32_t) * (size_t)nb));
-                            c->ticks_cap = nb;
-                        }
-                        const uint64_t key = schedule_key(rp, kw);
-                        c->sched_src = PBRT_SCHED_LAUNCH_ORDER;
-                        if (!(c->order_key == key && (int64_t)c->h_slot_order.size() == nb) && ci_order_cache(c)) {
-                            SchedEntry e;   // a fresh context: another context's measured order for this scene
-                            if (sched_cache_get(c, key, nb, e)) {
-                                c->h_slot_order = std::move(e.order);
-                                c->heavy_k = e.heavy_k;
-                                c->order_key = key;
-                                c->sched_src = PBRT_SCHED_CACHED;
-                            }
-                        }
-                        if (c->order_key == key && (int64_t)c->h_slot_order.size() == nb) {
-                            if (c->sched_src != PBRT_SCHED_CACHED) c->sched_src = PBRT_SCHED_LEARNED;
-                            HIPCHK(c, hipMemcpyAsync(c->d_slot_order, c->h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
-                                                     hipMemcpyHostToDevice, c->stream));
-                            order = c->d_slot_order;
-                            learned = true;
-                        }
-                        c->probed = false;
-                        if (!order && ci_probe_enabled(c) && nb <= (int64_t)1 << 24) {
-                            // no measured order for this configuration yet: estimate it
-                            int64_t npad = 2048;
-                            while (npad < nb) npad <<= 1;
-                            if (c->cost_cap < npad) {
-                                if (c->d_cost) (void)hipFree(c->d_cost);
-                                if (c->d_cost_keys) (void)hipFree(c->d_cost_keys);
-                                c->d_cost = nullptr;
-                                c->d_cost_keys = nullptr;
-                                c->cost_cap = 0;
-                                HIPCHK(c, hipMalloc((void**)&c->d_cost, sizeof(float) * 4 * (size_t)npad));
-                                HIPCHK(c, hipMalloc((void**)&c->d_cost_keys, sizeof(uint64_t) * (size_t)npad));
-                                c->cost_cap = npad;
-                            }
-                            HIPCHK(c, hipMemsetAsync(c->d_cost_keys, 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
-                            launch_k(c, kx ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)nb),
-                                               dim3(kWave), 0, c->stream, with_slot(sc, 0),
-                                               rp, c->wb, sb, nb, c->d_cost, c->d_cost_keys);
-                            bitonic_sort_u64(c->d_cost_keys, (uint32_t)npad, c->stream, &c->log_frame);
-                            launch_k(c, k_order_of_keys, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0,
-                                               c->stream, c->d_cost_keys, nb, c->d_slot_order);
-                            order = c->d_slot_order;
-                            c->probed = true;
-                            c->sched_src = PBRT_SCHED_PROBE;
-                            c->cost_n = nb;
-                        }
-                        ticks = c->d_ticks;
-                        c->ticks_pending = true;
-                        c->ticks_key = key;
-                        c->ticks_n = nb;
-                    }
-                    // one launch of n workgroups, workgroup b on slot ord[b] (identity if null)
-                    bool split_launch = false;   // launch_ci's launch is the heavy half of a split
-                    // waves per tile of a split's light launch
-                    // (set below, before any launch_ci call)
-                    bool light_kw = kw > 1 && c->knobs.ci_light_kw;
-                    int light_w = light_kw ? kw : 1;
-                    int heavy_w = ci_heavy_waves(c);
-                    auto launch_ci = [&](int w, int64_t n, const uint32_t* ord, hipStream_t st, uint32_t* prog) {
-                        if (w > 1) {   // one tile per workgroup of w waves; the ring grows with the lanes
-                            const int ring = w * kCiRingBytes / (int)sizeof(RingEnt);
-                            unsigned lds = 0;
-                            // next-pixel speculation (k_chain_ci kNps: Matte, stride 1) for launches of
-                            // multi-wave tiles only: not for the heavy launch of a split, where
-                            // its two rings' LDS cost the light tiles beside it (1/4 shard of B
-                            // 132 -> 145 ms; a 1/8 shard, no split: 131.5 -> 127.2 ms)
-                            RenderParams rpl = rp;
-                            rpl.ci_nps = (!kx && (!split_launch || light_kw) && ci_stride(c, w) == 1) ? c->knobs.ci_nps : 0;
-                            const ChainLayout lw = ci_layout(c->lay_ci, w, 1, lds, rpl.ci_nps > 0);
-                            // kX: at most 4 waves per tile (ci_waves, ci_heavy_waves). The kX stack chains
-                            // (here and kern1 below) are compiled with use_lds_nodes = 0: select them by
-                            // !lds_nodes only, stage_nodes' own test, never for a tree that is staged
-                            auto kern = kx ? (w == 2 ? (lds_nodes ? k_chain_ci<2, 0, true> : k_chain_ci<2, 64, true>)
-                                                     : (lds_nodes ? k_chain_ci<4, 0, true> : k_chain_ci<4, 64, true>))
-                                        : mesh_only ? (w == 2 ? k_chain_ci<2, -1> : w == 4 ? k_chain_ci<4, -1> : k_chain_ci<8, -1>)
-                                        : rp.sp_window ? (w == 2 ? k_chain_ci<2, 0, false, 0, true>
-                                                          : w == 4 ? k_chain_ci<4, 0, false, 0, true>
-                                                                   : k_chain_ci<8, 0, false, 0, true>)
-                                           : (w == 2   ? (lds_nodes ? k_chain_ci<2> : k_chain_ci<2, 64>)
-                                              : w == 4 ? (lds_nodes ? k_chain_ci<4> : k_chain_ci<4, 64>)
-                                                       : (lds_nodes ? k_chain_ci<8> : k_chain_ci<8, 64>));
-                            launch_k(c, kern, dim3((unsigned)n), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
-                                               c->d_jump, c->wb, sb, nb, kWave * w, ring, c->d_ctr, ord, ticks,
-                                               ci_stride(c, w), prog);
-                        } else {
-                            const int Gc = std::min(G, kCiMaxGroups);
-                            const int ring = kCiRingBytes / (int)sizeof(RingEnt) / Gc;
-                            unsigned lds = 0;
-                            const ChainLayout lw = ci_layout(c->lay_ci, 1, Gc, lds);
-                            // Matte analytic scenes: the 3-waves/SIMD build unless the
-                            // workgroup's LDS (large spp: StartPixel staging) caps the CU
-                            // below 3 waves/SIMD, where the 2-wave build (no spills) is faster
-                            // (config C: 6.53 vs 7.41 s)
-                            const bool eu2 = !kx && !mesh_only &&
-                                             (c->knobs.ci_eu == 2 ||
-                                              (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes, Gc > 1)));
-                            c->ci_wps = (kx || eu2) ? 2 : 3;
-                            // one tile per wave: the group's state in scalar registers;
-                            // several (opts.lanes_per_wave): the per-lane kMulti instantiations.
-                            // The one-wave kX chain runs the per-lane code at one tile per wave
-                            // too (lanes_per_tile = 64): with the scalar state config G measured
-                            // 473.5 against 471.5 ms (profiles/chain_sgpr/), so kX has no other
-                            // one-wave instantiation
-                            auto kern1 = kx ? (lds_nodes ? k_chain_ci<1, 0, true, 0, false, true>
-                                                         : k_chain_ci<1, 64, true, 0, false, true>)
-                                : Gc > 1
-                                ? (mesh_only ? k_chain_ci<1, -1, false, 0, false, true>
-                                   : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true, true> : k_chain_ci<1, 0, false, 0, true, true>)
-                                   : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2, false, true> : k_chain_ci<1, 64, false, 2, false, true>)
-                                         : (lds_nodes ? k_chain_ci<1, 0, false, 0, false, true> : k_chain_ci<1, 64, false, 0, false, true>))
-                                : (mesh_only ? k_chain_ci<1, -1>
-                                   : rp.sp_window ? (eu2 ? k_chain_ci<1, 0, false, 2, true> : k_chain_ci<1, 0, false, 0, true>)
-                                   : eu2 ? (lds_nodes ? k_chain_ci<1, 0, false, 2> : k_chain_ci<1, 64, false, 2>)
-                                         : (lds_nodes ? k_chain_ci<1> : k_chain_ci<1, 64>));
-                            launch_k(c, kern1, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave),
-                                               lds, st, with_slot(sc, 2), rp, lw, c->d_jump, c->wb, sb,
-                                               nb, kWave / Gc, ring, c->d_ctr, Gc == 1 ? ord : nullptr,
-                                               Gc == 1 ? ticks : nullptr, ci_stride(c, 1), prog);
-                        }
-                    };
-                    // the heaviest tiles of the last frame get 4 waves each; they are
-                    // launched first, on the main stream, and the rest concurrently on
-                    // stream2 (same-stream launches would serialise)
-                    // (multi-GPU shards, where kw > 1: the rest then run at 1 wave per
-                    // tile, the most efficient per lane)
-                    // measured wins at 1/2 and 1/4 shards (nb > n_simd); a loss at 1/8
-                    // (1020 tiles: 294 -> 307 ms), so smaller launches never split
-                    // one GPU (kw == 1): since the Matte chain runs 3 waves/SIMD the whole
-                    // frame's lane time is below its heaviest tile's chain, so the heaviest
-                    // tiles get 4 waves there too (config B: chain 328.5 -> 313.3 ms)
-                    // (measured a loss on the mesh chain, D 825 -> 920 ms, and on kX, G 509 -> 517 ms:
-                    // one GPU splits only the 3-wave Matte analytic chain)
-                    bool split1 = false;
-                    if (kw == 1 && G == 1 && !kx && !mesh_only) {
-                        unsigned lds1 = 0;
-                        (void)ci_layout(c->lay_ci, 1, 1, lds1);
-                        split1 = ci_eu3_fits(c, lds1, lds_nodes);
-                    }
-                    int64_t heavy = (learned && G == 1 && (kw > 1 ? nb > c->n_simd : split1) && ci_split_enabled(c))
-                                        ? std::min<int64_t>(c->heavy_k, nb) : 0;
-                    if (ci_heavy_override(c) >= 0 && learned && G == 1)   // tests and experiments force the split
-                        heavy = std::min<int64_t>(ci_heavy_override(c), nb);
-                    // a multi-wave Matte shard that fits the wave slots (1/8 of B: 1020 tiles at 4 waves)
-                    // is bound by its heaviest tiles' pixel-serial chains: those at 8 waves, the
-                    // rest at kw, next-pixel speculation in both (the N=8 shards' max 121.9 ->
-                    // ~107 ms with 32; 4-32 within a few ms; all tiles at 8 waves: 178 ms)
-                    if (heavy == 0 && ci_heavy_override(c) < 0 && learned && G == 1 && kw > 1 && nb <= c->n_simd &&
-                        !kx && !mesh_only && ci_split_enabled(c) && c->knobs.ci_split8 > 0) {
-                        heavy = std::min<int64_t>(c->knobs.ci_split8, nb / 16);
-                        light_kw = true;
-                        light_w = kw;
-                        heavy_w = 8;
-                    }
-                    if (heavy >= nb) heavy = 0;   // nothing left for the light launch: one launch at kw
-                    c->last_heavy = heavy;
-                    if (ticks) {   // label every slot with the waves it actually runs at
-                        c->h_slot_kw.assign((size_t)nb, (uint8_t)(heavy > 0 ? light_w : kw));
-                        for (int64_t i = 0; i < heavy; i++) c->h_slot_kw[c->h_slot_order[(size_t)i]] = (uint8_t)heavy_w;
-                    }
-                    // PBRT_PATHS_OVERLAP (a learned split, G == 1): the completion-driven path stage.
-                    //  - the heavy launch on the main stream (normal priority);
-                    //  - the light launch on stream3 (high priority: it wins every slot that frees
-                    //    while it has workgroups left), behind a k_gate that opens once every heavy
-                    //    workgroup has started, so it never delays a heavy tile's start;
-                    //  - the path stage on stream2 (normal priority): chunks of the tiles in their
-                    //    chains' completion order (k_chain_ci's completion list), each behind a k_gate
-                    //    that opens when its tiles' chains have ended. The chunks halve (1/2, 1/4, ...
-                    //    of the tiles; the last 1/2^(K-1)), so most path work is queued while the
-                    //    chains run and takes the slots they free once no chain workgroup waits.
-                    // Progress-driven, not timed (it replaces round 5's timed wait); only the
-                    // schedule changes, never a result.
-                    const bool ov_ok = c->knobs.paths_overlap > 0 && paths_ci_exact && learned && !c->ov_retry &&
-                                       c->ov_stalls < 2;
-                    const bool overlap = heavy > 0 && ov_ok;
-                    // no split: the one chain launch on stream3 (its workgroups win the slots the
-                    // path chunks also wait for); the completion list needs one tile per workgroup
-                    const bool overlap1 = heavy == 0 && ov_ok && c->knobs.paths_overlap_all && (kw > 1 || G == 1);
-                    if ((overlap || overlap1) && !c->stream3) {   // created on first use
-                        int least = 0, greatest = 0;
-                        HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-                        HIPCHK(c, hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, greatest));
-                        HIPCHK(c, hipEventCreateWithFlags(&c->ev_l2, hipEventDisableTiming));
-                        HIPCHK(c, hipEventCreateWithFlags(&c->ev_p1, hipEventDisableTiming));
-                    }
-                    if ((overlap || overlap1) && c->prog_cap < nb + kProgHead) {
-                        if (c->d_prog) (void)hipFree(c->d_prog);
-                        c->d_prog = nullptr;
-                        c->prog_cap = 0;
-                        HIPCHK(c, hipMalloc((void**)&c->d_prog, sizeof(uint32_t) * (size_t)(nb + kProgHead)));
-                        c->prog_cap = nb + kProgHead;
-                    }
-                    auto paths = [&]() -> int {   // the path chunks on stream2, each behind its k_gate
-                        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
-                        for (int64_t s0 = 0, j = 0; s0 < nb; j++) {
-                            const int64_t e0 = j + 1 >= c->knobs.paths_overlap ? nb
-                                                                              : s0 + std::max<int64_t>(1, (nb - s0) / 2);
-                            launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->d_prog, (uint32_t)s0,
-                                               (uint32_t)e0, c->d_ctr);
-                            launch_paths(c->d_prog + kProgHead + s0, e0 - s0, c->stream2);
-                            s0 = e0;
-                        }
-                        HIPCHK(c, hipEventRecord(c->ev_p1, c->stream2));
-                        return PBRT_OK;
-                    };
-                    if (overlap || overlap1) {
-                        HIPCHK(c, hipMemsetAsync(c->d_prog, 0, kProgHead * sizeof(uint32_t), c->stream));
-                        HIPCHK(c, hipMemsetAsync(c->d_prog + kProgHead, 0xFF, sizeof(uint32_t) * (size_t)nb, c->stream));
-                        HIPCHK(c, hipEventRecord(c->ev_split, c->stream));
-                    }
-                    if (overlap1) {
-                        HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_split, 0));
-                        launch_ci(kw, nb, order, c->stream3, c->d_prog);
-                        HIPCHK(c, hipGetLastError());
-                        HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
-                        const int r = paths();
-                        if (r != PBRT_OK) return r;
-                        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
-                        c->ov_done = nb;
-                    } else if (overlap) {
-                        split_launch = true;
-                        launch_ci(heavy_w, heavy, order, c->stream, c->d_prog);
-                        split_launch = false;
-                        HIPCHK(c, hipGetLastError());   // the gates below wait for these workgroups
-                        auto light = [&]() -> int {
-                            HIPCHK(c, hipStreamWaitEvent(c->stream3, c->knobs.gate_hold ? c->ev_p1 : c->ev_split, 0));
-                            launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream3, c->d_prog,
-                                               (uint32_t)heavy, (uint32_t)heavy, c->d_ctr);
-                            launch_ci(light_w, nb - heavy, order + heavy, c->stream3, c->d_prog);
-                            HIPCHK(c, hipGetLastError());
-                            HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
-                            return PBRT_OK;
-                        };
-                        const int r1 = c->knobs.gate_hold ? paths() : light();
-                        if (r1 != PBRT_OK) return r1;
-                        const int r2 = c->knobs.gate_hold ? light() : paths();
-                        if (r2 != PBRT_OK) return r2;
-                        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
-                        c->ov_done = nb;
-                    } else if (heavy > 0) {
-                        HIPCHK(c, hipEventRecord(c->ev_split, c->stream));
-                        split_launch = true;
-                        launch_ci(heavy_w, heavy, order, c->stream, nullptr);
-                        split_launch = false;
-                        HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
-                        launch_ci(light_w, nb - heavy, order + heavy, c->stream2, nullptr);
-                        HIPCHK(c, hipEventRecord(c->ev_join, c->stream2));
-                        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_join, 0));
-                    } else {
-                        launch_ci(kw, nb, order, c->stream, nullptr);
-                    }
-                }
-                HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
-                if (c->use_dl) {
-                    const int64_t nrec = nb * c->wb.ppt;
-                    if (rp.spp > 1)
-                        launch_k(c, kx ? k_dl_samples<true> : k_dl_samples<false>,
-                                           dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave,
-                                                                            (int64_t)c->n_simd * 64)),
-                                           dim3(kWave), 0, c->stream, with_slot(sc, 3), rp, c->wb, sb, nrec);
-                    launch_k(c, k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp,
-                                       c->wb, sb, nrec, c->d_ctr);
-                } else if (paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0) {
-                    // the path wavefront: mesh scenes, and whatever k_paths_ci cannot
-                    // take (a tree beyond LDS, more than 64 / P lights)
-                    if (rp.mode == PBRT_MODE_THROUGHPUT)
-                        launch_k(c, kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)), dim3(kWave),
-                                           (unsigned)c->lay.total, c->stream, with_slot(sc, 4), rp, c->lay, c->d_jump,
-                                           c->wb, sb, nb);
-                    const int rcp = paths_wavefront(c, with_slot(sc, rp.mode == PBRT_MODE_THROUGHPUT ? 5 : 3), sb, nb);
-                    if (rcp != PBRT_OK) return rcp;
-                } else if (rp.mode == PBRT_MODE_THROUGHPUT && paths_ci_pixels(c, rp) > 0) {
-                    // setup (StartPixel + bounce 1 per pixel), then lane-refill paths
-                    launch_k(c, kx ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(nb * c->wb.ppt)),
-                                       dim3(kWave), (unsigned)c->lay.total, c->stream, with_slot(sc, 4), rp, c->lay,
-                                       c->d_jump, c->wb, sb, nb);
-                    const int pp = paths_ci_pixels(c, rp);
-                    const int per = rp.ndims * rp.spp;
-                    auto kern = kx ? (pp == 8 ? k_paths_ci<8, true, true> : k_paths_ci<4, true, true>)
-                                   : (pp == 8 ? k_paths_ci<8, true> : pp == 2 ? k_paths_ci<2, true> : k_paths_ci<4, true>);
-                    const int sl = paths_ci_s1d_lds(c, rp, pp) ? 1 : 0;
-                    const int lds = pp == 8 ? paths_group_lds<8>(sl * per) : pp == 2 ? paths_group_lds<2>(sl * per)
-                                                                                     : paths_group_lds<4>(sl * per);
-                    launch_k(c, kern, dim3((unsigned)((nb * c->wb.ppt + pp - 1) / pp)), dim3(kWave),
-                                       (unsigned)lds, c->stream, with_slot(sc, 5), rp, c->wb, sb, nb * c->wb.ppt,
-                                       c->d_ctr, sl, nullptr);
-                }
-                else if (c->ov_done > 0) {   // the completion-driven path stage (stream2) ends the chain stage
-                    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_p1, 0));
-                } else {
-                    launch_paths(nullptr, nb, c->stream);
-                }
-                HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
-                launch_k(c, k_film, dim3((unsigned)nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
-                                   c->d_film, rp, c->wb, sb, nb, c->d_films, c->d_cancel_seen, c->d_ctr);
-                launch_k(c, k_panic_reduce, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, c->stream, c->wb,
-                                   sb, nb, c->d_panics, c->d_ctr);
-
-            }
+        if (c->use_cam || c->use_spec) {
+            if ((rc = c->use_cam ? enqueue_cam(c, sc) : enqueue_wave(c, sc)) != PBRT_OK) return rc;
         } else {
             c->last_kernel = PBRT_KERNEL_SERIAL;
             c->n_batches = 0;
-            int64_t blocks = (rp.n_slots + rp.lanes_per_wave - 1) / rp.lanes_per_wave;
-            auto kern = k_render_exact<1>;
-            if (c->min_waves == 2) kern = k_render_exact<2>;
-            else if (c->min_waves == 4) kern = k_render_exact<4>;
-            else if (c->min_waves == 8) kern = k_render_exact<8>;
+            const int64_t blocks = (rp.n_slots + rp.lanes_per_wave - 1) / rp.lanes_per_wave;
+            const SerialKernel kern = serial_kernel(c->min_waves);
+            if (!kern)
+                return set_err(c, PBRT_E_HIP, "no k_render_exact instantiation for occupancy " + std::to_string(c->min_waves));
             launch_k(c, kern, dim3((unsigned)blocks), dim3(kWave), 0, c->stream, with_slot(sc, 6), rp, c->d_films,
-                               c->d_s1d, c->d_panics, c->d_ctr);
+                     c->d_s1d, c->d_panics, c->d_ctr);
         }
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     int64_t npx = rp.film_w * rp.film_h;
     launch_k(c, k_merge_film, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film, rp,
-                       c->d_films, out, c->d_cancel_seen);
+             c->d_films, out, c->d_cancel_seen);
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev2, c->stream));
     c->rendered = true;
@@ -2449,74 +2545,17 @@ extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
 
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
 // kernel the library compiles, spelled as its explicit instantiation is
-// (tests/test_kernel_manifest.py compares this table with the sources).
+// (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
+// k_paths_ci and k_paths_cam[_stack] families are named by their selectors' tables.
 namespace {
 const KernelName kKernelNames[] = {
-    // k_chain_1.hip
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 2, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, true, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, true, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, -1, false, 0, false, false>),
-    // k_chain_n.hip
-    PBRT_KERNEL_NAME(k_chain_ci<2, 0, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<2, 64, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, 0, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, 64, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<8, 0, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<8, 64, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<2, 0, false, 0, true, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, 0, false, 0, true, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<8, 0, false, 0, true, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<2, -1, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, -1, false, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<8, -1, false, 0, false, false>),
-    // k_chain_x.hip
-    PBRT_KERNEL_NAME(k_chain_ci<2, 0, true, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, 0, true, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<2, 64, true, 0, false, false>),
-    PBRT_KERNEL_NAME(k_chain_ci<4, 64, true, 0, false, false>),
-    // k_chain_g.hip
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 2, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 64, false, 0, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 0, true, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, false, 2, true, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, -1, false, 0, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 0, true, 0, false, true>),
-    PBRT_KERNEL_NAME(k_chain_ci<1, 64, true, 0, false, true>),
     // k_paths_m.hip, k_paths_x.hip
-    PBRT_KERNEL_NAME(k_paths_ci<2, false, false>),
-    PBRT_KERNEL_NAME(k_paths_ci<4, false, false>),
-    PBRT_KERNEL_NAME(k_paths_ci<8, false, false>),
-    PBRT_KERNEL_NAME(k_paths_ci<2, true, false>),
-    PBRT_KERNEL_NAME(k_paths_ci<4, true, false>),
-    PBRT_KERNEL_NAME(k_paths_ci<8, true, false>),
     PBRT_KERNEL_NAME(k_mb_setup<false>),
-    PBRT_KERNEL_NAME(k_paths_ci<4, false, true>),
-    PBRT_KERNEL_NAME(k_paths_ci<8, false, true>),
-    PBRT_KERNEL_NAME(k_paths_ci<4, true, true>),
-    PBRT_KERNEL_NAME(k_paths_ci<8, true, true>),
     PBRT_KERNEL_NAME(k_mb_setup<true>),
     // k_chain_c.hip, k_paths_c.hip
     PBRT_KERNEL_NAME(k_chain_cam),
     PBRT_KERNEL_NAME(k_cam_setup),
-    PBRT_KERNEL_NAME(k_paths_cam<4, false>),
-    PBRT_KERNEL_NAME(k_paths_cam<16, false>),
-    PBRT_KERNEL_NAME(k_paths_cam<64, false>),
-    PBRT_KERNEL_NAME(k_paths_cam<4, true>),
-    PBRT_KERNEL_NAME(k_paths_cam<16, true>),
-    PBRT_KERNEL_NAME(k_paths_cam<64, true>),
     PBRT_KERNEL_NAME(k_chain_cam_stack),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<4, false>),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<16, false>),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<64, false>),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<4, true>),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<16, true>),
-    PBRT_KERNEL_NAME(k_paths_cam_stack<64, true>),
     PBRT_KERNEL_NAME(k_film_cam<false>),
     PBRT_KERNEL_NAME(k_film_cam<true>),
     // k_serial.hip
@@ -2566,28 +2605,46 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_query_camera),
     PBRT_KERNEL_NAME(k_probe),
 };
-constexpr size_t kNKernelNames = sizeof(kKernelNames) / sizeof(kKernelNames[0]);
 
-const char* kernel_name_of(const void* fn) {
-    for (size_t i = 0; i < kNKernelNames; i++)
-        if (kKernelNames[i].fn == fn) return kKernelNames[i].name;
+template <class F>
+void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' tables, kKernelNames, the LBVH unit's
+    for (const ChainRow& r : kChainKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const PathsCiRow& r : kPathsCiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const KernelName& k : kKernelNames) f(k.fn, k.name);
     size_t nm = 0;
     const KernelName* mk = mesh_bvh_kernel_names(&nm);
-    for (size_t i = 0; i < nm; i++)
-        if (mk[i].fn == fn) return mk[i].name;
-    return "?";
+    for (size_t i = 0; i < nm; i++) f(mk[i].fn, mk[i].name);
+}
+const char* kernel_name_of(const void* fn, const char* unknown = "?") {
+    const char* name = unknown;
+    each_kernel([&](const void* f, const char* n) { if (f == fn) name = n; });
+    return name;
 }
 }  // namespace
 
 extern "C" int pbrt_gpu_kernel_names(const char** out, int n) {
-    size_t nm = 0;
-    const KernelName* mk = mesh_bvh_kernel_names(&nm);
     int k = 0;
-    for (size_t i = 0; i < kNKernelNames; i++, k++)
-        if (out && k < n) out[k] = kKernelNames[i].name;
-    for (size_t i = 0; i < nm; i++, k++)
-        if (out && k < n) out[k] = mk[i].name;
+    each_kernel([&](const void*, const char* name) {
+        if (out && k < n) out[k] = name;
+        k++;
+    });
     return k;
+}
+
+extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a, int n) {
+    if (!family || !a) return nullptr;
+    const std::string f = family;
+    const void* fn = nullptr;
+    if (f == "k_chain_ci" && n == 6)
+        fn = reinterpret_cast<const void*>(chain_kernel(a[0], a[1], a[2] != 0, a[3], a[4] != 0, a[5] != 0));
+    else if (f == "k_paths_ci" && n == 3)
+        fn = reinterpret_cast<const void*>(paths_ci_kernel(a[0], a[1] != 0, a[2] != 0));
+    else if (f == "k_paths_cam" && n == 3)
+        fn = reinterpret_cast<const void*>(paths_cam_kernel(a[0], a[1] != 0, a[2] != 0));
+    else if (f == "k_render_exact" && n == 1)
+        fn = reinterpret_cast<const void*>(serial_kernel(a[0]));
+    return fn ? kernel_name_of(fn, nullptr) : nullptr;
 }
 
 extern "C" int64_t pbrt_gpu_launch_log(pbrt_gpu_ctx* c, int which, pbrt_launch_rec* out, int64_t n, uint64_t* overflow) {

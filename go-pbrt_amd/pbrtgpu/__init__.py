@@ -183,6 +183,15 @@ def kernel_names():
     return [s.decode() for s in out]
 
 
+def kernel_choice(family, *args):
+    """The kernel render.hip's selector of `family` gives for these template arguments, by its
+    launch-log name, or None if it is not compiled (pbrt_diag_kernel_choice; needs no GPU)."""
+    abi.declare_kernel_choice(lib())
+    a = (C.c_int * max(len(args), 1))(*[int(x) for x in args])
+    name = lib().pbrt_diag_kernel_choice(family.encode(), a, len(args))
+    return name.decode() if name is not None else None
+
+
 class Launch(tuple):
     """One record of the launch log: (name, grid, block, lds, stream); grid and block
     are 3-tuples, lds the dynamic LDS bytes, stream 0 (the context's main stream), 2

@@ -309,6 +309,13 @@ def declare_launch_log(L):
     L.pbrt_gpu_lds_per_block.restype = C.c_int64
 
 
+def declare_kernel_choice(L):
+    """ctypes prototype of pbrt_diag_kernel_choice (include/pbrt_diag.h). Apart from the other
+    prototypes: a library of an earlier build (PBRT_GPU_LIB) loads without this entry."""
+    L.pbrt_diag_kernel_choice.argtypes = [C.c_char_p, C.POINTER(C.c_int), C.c_int]
+    L.pbrt_diag_kernel_choice.restype = C.c_char_p
+
+
 PBRT_GROUP_MAX = 8
 
 

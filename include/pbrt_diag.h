@@ -136,6 +136,17 @@ int64_t pbrt_gpu_launch_log(struct pbrt_gpu_ctx* ctx, int which, pbrt_launch_rec
 /* Every name the log can produce (needs no GPU). Copies min(n, names) pointers
  * and returns the name count. */
 int pbrt_gpu_kernel_names(const char** out, int n);
+/* The answer of render.hip's kernel selectors, which every launch of a templated
+ * family goes through (needs no context and no GPU): the launch-log name of the
+ * instantiation with exactly the template arguments `args`, or NULL if no unit
+ * compiles it (a launch site then refuses with PBRT_E_HIP). Families and their n
+ * arguments (booleans as 0 / 1):
+ *   "k_chain_ci"     6: waves, depth (-1, 0, 64), kx, eu (0, 2), spwin, multi
+ *   "k_paths_ci"     3: P, mb, kx
+ *   "k_paths_cam"    3: P, mb, stack (1: k_paths_cam_stack)
+ *   "k_render_exact" 1: min_waves
+ * NULL for any other family or argument count. */
+const char* pbrt_diag_kernel_choice(const char* family, const int* args, int n);
 /* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */
 int64_t pbrt_gpu_lds_per_block(struct pbrt_gpu_ctx* ctx);
 

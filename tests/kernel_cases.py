@@ -8,9 +8,10 @@ tests/test_kernel_manifest.py (no GPU) holds COVERAGE + EXEMPT equal to the
 manifest; tests/test_gpu_kernel_coverage.py renders every case twice against
 the oracle and finds the kernels in the launch log.
 
-The launch decision each case steers is render.hip's (launch_ci, launch_paths,
-enqueue_cam, paths_wavefront, the serial launch); the comment of a case says
-which condition selects its kernel.
+The launch decision each case steers is render.hip's: the arguments launch_ci,
+launch_paths, enqueue_cam and the serial launch give their kernel selectors
+(chain_kernel, paths_ci_kernel, paths_cam_kernel, serial_kernel), and
+paths_wavefront; the comment of a case says which condition selects its kernel.
 """
 from collections import namedtuple
 
