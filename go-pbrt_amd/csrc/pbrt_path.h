@@ -16,6 +16,7 @@
 #pragma once
 #pragma clang fp contract(off)
 
+#include "bvh_tables.h"
 #include "pbrt_core.h"
 #include "pbrt_mesh.h"
 #include "sphere_filter.h"
@@ -527,8 +528,8 @@ struct NodeView {
     uint32_t offset, n_prims, axis;
 };
 // BVH nodes staged in LDS by kernels whose scene fits (README / Cornell:
-// <= 45 nodes). A file-scope __shared__ array, so every access is a ds_read.
-constexpr int kLdsNodes = 64;
+// <= 45 nodes; kLdsNodes, bvh_tables.h). A file-scope __shared__ array, so every
+// access is a ds_read.
 __shared__ DevNode g_nodes_lds[kLdsNodes];
 
 __device__ __forceinline__ NodeView load_node(const DevScene& sc, uint32_t i) {
@@ -578,22 +579,17 @@ __device__ __forceinline__ bool node_hit(const NodeView& nd, const Ray& r, V3 in
 }
 
 // Preorder visit table of the BVH, one per ray-direction octant (built on the
-// host, dev_order in render.hip). The reference's traversal (bvh.go:659-765)
+// host, dev_order in scene_tables.h). The reference's traversal (bvh.go:659-765)
 // is a depth-first walk whose child order at an interior node depends only on
 // the sign of the ray direction along the node's split axis: for a given
 // octant it visits nodes in one fixed preorder, skipping the subtree of every
-// node whose box test fails. Entry i of an octant's table holds
-//   bits  0-14  the node index (pbrt_bvh_node order)
-//   bit   15    a hit at this interior node would push past the [64] stack
-//               (bvh.go:670: the reference panics there)
-//   bits 16-31  the table index that follows the node's subtree (its skip)
-constexpr uint32_t kOrdNode = 0x7FFFu, kOrdOverflow = 0x8000u;
+// node whose box test fails. An entry's fields: kOrdNode, kOrdOverflow and the
+// skip in bits 16-31 (bvh_tables.h).
 // Leaves only, per octant, in that preorder (LDS-staged trees).
 __shared__ uint16_t g_leaf_lds[8 * kLdsNodes];
 // Leaf culling groups (LDS-staged trees): boxes, and per octant the mask of
 // leaf positions (in that octant's leaf preorder) each group covers, plus the
-// mask of leaves tested unconditionally.
-constexpr int kMaxCullGroups = 16;
+// mask of leaves tested unconditionally (kMaxCullGroups, bvh_tables.h).
 __shared__ double g_grp_lds[kMaxCullGroups * 6];
 __shared__ uint32_t g_gmask_lds[8 * (kMaxCullGroups + 1)];
 

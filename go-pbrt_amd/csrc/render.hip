@@ -39,17 +39,18 @@
 #include <cstdio>
 #include <cstring>
 #include <string>
-#include <functional>
 #include <mutex>
-#include <unordered_map>
 #include <vector>
 
 #include "../../include/pbrt_gpu.h"
 #include "../../include/pbrt_diag.h"
 #include "../../include/pbrt_scene.h"
+#include "knobs.h"
 #include "mesh_bvh.h"
 #include "query_buffers.h"
 #include "render_kernels.h"
+#include "scene_tables.h"
+#include "schedule.h"
 
 using namespace pbrt;
 using namespace pbrtk;
@@ -64,98 +65,67 @@ constexpr int kTickPlanes = 3;   // durations, start clocks, end clocks
 constexpr int kTickPlanes = 1;
 #endif
 
-// Experiment knobs (environment), read ONCE when a context is created
-// (pbrt_gpu_create), never per launch; defaults are the measured best.
-struct Knobs {
-    int ci_waves = 0;          // PBRT_CI_WAVES = 1, 2, 4, 8 (0: by tile count)
-    int ci_stride = 0;         // PBRT_CI_STRIDE = 1, 2 (0: 2 at one wave per tile, else 1)
-    int ci_heavy_waves = 4;    // PBRT_CI_HEAVY_WAVES = 4, 8
-    bool ci_light_kw = false;  // PBRT_CI_LIGHT_KW=1: a multi-wave shard's split runs its light tiles at the
-                               // shard's waves per tile (not 1), the heavy ones at PBRT_CI_HEAVY_WAVES
-    int ci_split8 = 32;        // PBRT_CI_SPLIT8=K: a learned multi-wave Matte shard that fits the wave slots
-                               // (no split otherwise: 1/8 of B) runs its K heaviest tiles (at most 1/16 of
-                               // them) at 8 waves beside the rest at its waves per tile; 0: off
-    int ci_eu = 0;             // PBRT_CI_EU = 2 / 3: the one-wave Matte chain's build (waves/SIMD its registers
-                               // are budgeted for); 0: by the workgroup's LDS (ci_eu3_fits)
-    int64_t ci_heavy = -1;     // PBRT_CI_HEAVY = K forces the heavy tile count (tests)
-    bool ci_split = true;      // PBRT_CI_SPLIT=0
-    bool ci_order = true;      // PBRT_CI_ORDER=0
-    bool ci_probe = true;      // PBRT_CI_PROBE=0
-    bool ci_order_cache = true;// PBRT_CI_ORDER_CACHE=0
-    bool sp_window = true;     // PBRT_SP_WINDOW=0: the lane-0 StartPixel replay instead of the windowed one
-    int ci_scap = -1;          // PBRT_CI_SCAP=Z: k_chain_ci's statistical speculation cap at Z/10 sigmas (0: off;
-                               // -1: the kernel's default, 1.5 sigma for mesh scenes; multi-wave tiles with
-                               // next-pixel speculation always use 3)
-    int ci_nps = 8;            // PBRT_CI_NPS=K: next-pixel speculation in multi-wave k_chain_ci tiles from K
-                               // samples before a pixel's end (0: off)
-    int paths_overlap = 5;     // PBRT_PATHS_OVERLAP=K: a split frame's path stage runs in K chunks of the
-                               // tiles in their chains' completion order, each released when its tiles'
-                               // chains have ended (render_enqueue; 0: off, the path stage after the chains)
-    bool paths_overlap_all = true;    // PBRT_PATHS_OVERLAP_ALL=0: the completion-driven path stage only for
-                               // split frames (measured on: C 5056 -> 4603 ms, G 495 -> 472 ms, the
-                               // N=8 shards' max 128.6 -> 119.7 ms)
-    bool gate_hold = false;    // PBRT_GATE_HOLD=1 (tests): the light chain launch waits for the path stage,
-                               // as a dispatcher that serialises kernels across streams may order them;
-                               // k_gate's stall exit and the re-render recover the frame
-    bool paths_s1d_lds = false;// PBRT_PATHS_S1D=lds
-    int paths_ci = -1;         // PBRT_PATHS_CI = 0, 2, 4, 8 (-1: auto)
-    int paths_wf = -1;         // PBRT_PATHS_WF = 0 / 1 (-1: mesh scenes)
-    bool pw_sort = false;      // PBRT_PW_SORT=1
-    double pw_gb = 24.0;       // PBRT_PW_GB
-    double wave_buffer_gb = 0; // PBRT_WAVE_BUFFER_GB (0: min(96 GB, half the free HBM))
-    bool ci_dense = false;     // PBRT_CI_DENSE=1 (builds with -DPBRT_CI_DENSE_WALK): k_chain_ci's closest hit by
-                               // bvh_walk_dense (bit-exact; slower on B)
-    int cull_group = 4;        // PBRT_CULL_GROUP: leaves per culling group
-    int cull_min = 2;          // PBRT_CULL_MIN
-    bool cull_groups = true;   // PBRT_CULL_GROUPS=0
-    static Knobs from_env() {
-        Knobs k;
-        auto ival = [](const char* n, int& out) { if (const char* e = getenv(n)) out = atoi(e); };
-        if (const char* e = getenv("PBRT_CI_WAVES")) {
-            const int v = atoi(e);
-            if (v == 1 || v == 2 || v == 4 || v == 8) k.ci_waves = v;
-        }
-        if (const char* e = getenv("PBRT_CI_STRIDE")) {
-            const int v = atoi(e);
-            if (v == 1 || v == 2) k.ci_stride = v;
-        }
-        if (const char* e = getenv("PBRT_CI_HEAVY_WAVES")) k.ci_heavy_waves = atoi(e) == 8 ? 8 : 4;
-        if (const char* e = getenv("PBRT_CI_LIGHT_KW")) k.ci_light_kw = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_SPLIT8")) k.ci_split8 = std::max(0, atoi(e));
-        if (const char* e = getenv("PBRT_CI_EU")) k.ci_eu = (atoi(e) == 2 || atoi(e) == 3) ? atoi(e) : 0;
-        if (const char* e = getenv("PBRT_CI_HEAVY")) k.ci_heavy = (int64_t)atoll(e);
-        if (const char* e = getenv("PBRT_CI_SPLIT")) k.ci_split = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_DENSE")) k.ci_dense = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_ORDER")) k.ci_order = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_PROBE")) k.ci_probe = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_ORDER_CACHE")) k.ci_order_cache = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_SP_WINDOW")) k.sp_window = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_CI_NPS")) k.ci_nps = std::max(0, atoi(e));
-        if (const char* e = getenv("PBRT_CI_SCAP")) k.ci_scap = std::max(-1, atoi(e));
-        if (const char* e = getenv("PBRT_PATHS_OVERLAP")) k.paths_overlap = std::min(std::max(0, atoi(e)), 16);
-        if (const char* e = getenv("PBRT_PATHS_OVERLAP_ALL")) k.paths_overlap_all = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_GATE_HOLD")) k.gate_hold = atoi(e) != 0;
-        if (const char* e = getenv("PBRT_PATHS_S1D")) k.paths_s1d_lds = std::strcmp(e, "lds") == 0;
-        if (const char* e = getenv("PBRT_PATHS_CI")) {
-            const int v = atoi(e);
-            if (v == 0 || v == 2 || v == 4 || v == 8) k.paths_ci = v;
-        }
-        if (const char* e = getenv("PBRT_PATHS_WF")) k.paths_wf = atoi(e) == 1 ? 1 : 0;
-        if (const char* e = getenv("PBRT_PW_SORT")) k.pw_sort = atoi(e) == 1;
-        if (const char* e = getenv("PBRT_PW_GB")) k.pw_gb = atof(e) > 0 ? atof(e) : k.pw_gb;
-        if (const char* e = getenv("PBRT_WAVE_BUFFER_GB")) k.wave_buffer_gb = atof(e) > 0 ? atof(e) : 0;
-        if (const char* e = getenv("PBRT_CULL_GROUP")) k.cull_group = std::max(2, atoi(e));
-        if (const char* e = getenv("PBRT_CULL_MIN")) k.cull_min = std::max(0, atoi(e));
-        int cg = 1;
-        ival("PBRT_CULL_GROUPS", cg);
-        k.cull_groups = cg != 0;
-        return k;
+namespace {
+int set_err(pbrt_gpu_ctx* c, int code, const std::string& m);
+}
+#define HIPCHK(ctx, call)                                                                            \
+    do {                                                                                             \
+        hipError_t e_ = (call);                                                                      \
+        if (e_ != hipSuccess)                                                                        \
+            return set_err(ctx, PBRT_E_HIP, std::string(#call ": ") + hipGetErrorString(e_));      \
+    } while (0)
+
+// The one owner of a device allocation: freed with its owner (the context, or a
+// scope). Errors go to the context `c` (null outside one).
+template <class T>
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p_, o.p_);
+        std::swap(cap_, o.cap_);
+        return *this;
     }
+    ~DevBuf() { release(); }
+    T* get() const { return p_; }
+    size_t cap() const { return cap_; }   // elements it has room for
+    // room for n elements: kept if it has them, else freed and allocated anew (the contents are lost)
+    int ensure(pbrt_gpu_ctx* c, size_t n) {
+        if (cap_ >= n && p_) return PBRT_OK;
+        release();
+        HIPCHK(c, hipMalloc((void**)&p_, sizeof(T) * (n ? n : 1)));
+        cap_ = n;
+        return PBRT_OK;
+    }
+    // a fresh allocation of n elements (an empty array keeps a valid pointer), filled from src unless null
+    int upload(pbrt_gpu_ctx* c, const T* src, size_t n) {
+        if (n == 0) n = 1;
+        release();
+        HIPCHK(c, hipMalloc((void**)&p_, sizeof(T) * n));
+        cap_ = n;
+        if (src) HIPCHK(c, hipMemcpy(p_, src, sizeof(T) * n, hipMemcpyHostToDevice));
+        return PBRT_OK;
+    }
+
+  private:
+    void release() {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    T* p_ = nullptr;
+    size_t cap_ = 0;   // elements
 };
 
 struct pbrt_gpu_ctx {
     Knobs knobs;
     int device = 0;
+    struct {
+        int n_simd = 1024;                 // SIMDs of the device (4 per CU)
+        size_t lds_per_block = 65536;      // the device's LDS limit per workgroup (sharedMemPerBlock)
+        size_t lds_per_cu = 160 * 1024;    // LDS of a CU (maxSharedMemoryPerMultiProcessor)
+    } dev;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     // heavy/light split of k_chain_ci: the heaviest tiles with 4 waves each on
@@ -165,24 +135,43 @@ struct pbrt_gpu_ctx {
     // PBRT_PATHS_OVERLAP: a high-priority stream for the light chain launch, the
     // events of the completion-driven path stage, and k_chain_ci's progress record
     // (layout at kProgHead)
-    hipStream_t stream3 = nullptr;
-    hipEvent_t ev_l2 = nullptr, ev_p1 = nullptr;
-    int64_t ov_done = 0;                 // slots whose path stage was launched beside the chains
-    uint32_t* d_prog = nullptr;
-    size_t prog_cap = 0;
-    // a frame whose k_gate saw the chains stand still (a dispatcher that serialises
-    // kernels across streams) is rendered again without the overlap; two such
-    // frames in a row turn the overlap off for the context
-    pbrt_render_desc last_rd{};
-    double* last_film_device = nullptr;
-    int ov_stalls = 0;
-    bool ov_retry = false;
-    MeshBuild mesh;                      // triangle meshes + their LBVH (extension)
-    int64_t heavy_k = 0;                 // slots at the front of h_slot_order that get 4 waves
-    int ci_wps = 2;                      // waves/SIMD of the last one-wave k_chain_ci launch (3 or 2)
-    int64_t last_heavy = 0;              // heavy slots of the last EXACT launch (0: no split)
-    std::vector<uint32_t> h_last_ticks;  // per-slot chain ticks of the last EXACT frame
-    std::vector<uint8_t> h_slot_kw;      // waves per tile each slot ran with in the last frame
+    struct {
+        hipStream_t stream3 = nullptr;
+        hipEvent_t ev_l2 = nullptr, ev_p1 = nullptr;
+        int64_t done = 0;                // slots whose path stage was launched beside the chains
+        DevBuf<uint32_t> d_prog;
+        // a frame whose k_gate saw the chains stand still (a dispatcher that serialises
+        // kernels across streams) is rendered again without the overlap; two such
+        // frames in a row turn the overlap off for the context
+        pbrt_render_desc last_rd{};
+        double* last_film_device = nullptr;
+        int stalls = 0;
+        bool retry = false;
+    } ov;
+    MeshBuild mesh;                // triangle meshes + their LBVH (extension)
+    // k_chain_ci heaviest-first schedule: per-slot chain time of the last
+    // EXACT frame (wall_clock64 ticks) and the slot order derived from it
+    struct {
+        int64_t heavy_k = 0;                 // slots at the front of h_slot_order that get 4 waves
+        int ci_wps = 2;                      // waves/SIMD of the last one-wave k_chain_ci launch (3 or 2)
+        int64_t last_heavy = 0;              // heavy slots of the last EXACT launch (0: no split)
+        std::vector<uint32_t> h_last_ticks;  // per-slot chain ticks of the last EXACT frame
+        std::vector<uint8_t> h_slot_kw;      // waves per tile each slot ran with in the last frame
+        DevBuf<uint32_t> d_ticks;            // [kTickPlanes][slots]
+        std::vector<uint32_t> h_tick_clocks; // diagnostics builds: [start | end] clocks of the last frame
+        DevBuf<uint32_t> d_slot_order;
+        std::vector<uint32_t> h_slot_order;
+        uint64_t order_key = 0, ticks_key = 0;
+        int64_t ticks_n = 0;
+        bool ticks_pending = false;
+        int src = 0;                         // schedule of the last EXACT frame: PBRT_SCHED_* (pbrt_diag.h)
+        // cold-frame schedule (k_tile_cost): per-slot features and sort keys
+        DevBuf<float> d_cost;
+        DevBuf<uint64_t> d_cost_keys;
+        int64_t cost_n = 0;
+        bool probed = false;                 // the last EXACT frame ran the cost probe
+    } sched;
+    uint64_t scene_hash = 0;         // content hash of the scene (process-wide schedule cache)
     double* film_target = nullptr;   // caller buffer of the last render_async_into
     int lanes_per_wave = 64;
     bool lanes_per_wave_set = false;
@@ -190,20 +179,16 @@ struct pbrt_gpu_ctx {
     int occ_req = 0;        // opts.occupancy as given (0 = each kernel's default)
     int kernel_req = PBRT_KERNEL_AUTO;
     int last_kernel = 0;    // PBRT_KERNEL_SERIAL / PBRT_KERNEL_WAVE
-    PcgJump* d_jump = nullptr;
+    DevBuf<PcgJump> d_jump;
     pbrt_distribution_desc host_dist;
     // wave-parallel path (k_wf_primary, k_chain_ci, k_paths_ci / k_pw_*, k_film)
     ChainLayout lay{};
     bool use_spec = false;
-    unsigned char* d_wave = nullptr;   // per-batch pixel records, stratified values, RNG states, L
-    size_t wave_cap = 0;
+    DevBuf<unsigned char> d_wave;      // per-batch pixel records, stratified values, RNG states, L
     int64_t wave_batch = 0;            // tile slots per batch
     int tiles_per_wave = 1;            // k_chain_ci lane groups per wave (64 / lanes per tile)
     std::vector<hipEvent_t> bev;       // per batch: before the chain, after the chain, after the paths
     int n_batches = 0;
-    int n_simd = 1024;                 // SIMDs of the device (4 per CU)
-    size_t lds_per_block = 65536;      // the device's LDS limit per workgroup (sharedMemPerBlock)
-    size_t lds_per_cu = 160 * 1024;    // LDS of a CU (maxSharedMemoryPerMultiProcessor)
     WaveBufs wb{};
     bool use_ci = false;   // the Path chain stage (k_chain_ci)
     bool use_dl = false;   // DirectLighting on k_dl_setup / k_dl_samples
@@ -211,56 +196,33 @@ struct pbrt_gpu_ctx {
     bool use_cam = false;   // the camera-start route (PBRT_KERNEL_WAVE_CAM: k_chain_cam, k_paths_cam, k_film_cam)
     ChainLayout lay_cam{};
     // device scene
-    pbrt_shape_desc* d_shapes = nullptr;
-    pbrt_material_desc* d_materials = nullptr;
-    pbrt_primitive_desc* d_prims = nullptr;
-    DevNode* d_nodes = nullptr;
-    uint32_t* d_order = nullptr;     // [8][n_nodes] preorder visit tables, then [8][n_nodes] leaf lists (dev_order)
-    double* d_groups = nullptr;      // leaf culling groups (cull_groups)
-    uint32_t* d_gmasks = nullptr;
+    DevBuf<pbrt_shape_desc> d_shapes;
+    DevBuf<pbrt_material_desc> d_materials;
+    DevBuf<pbrt_primitive_desc> d_prims;
+    DevBuf<DevNode> d_nodes;
+    DevBuf<uint32_t> d_order;        // [8][n_nodes] preorder visit tables, then [8][n_nodes] leaf lists (dev_order)
+    DevBuf<double> d_groups;         // leaf culling groups (cull_groups)
+    DevBuf<uint32_t> d_gmasks;
     int n_groups = 0;
     std::vector<int> h_node_prims;   // nPrimitives per node (leaf count for DevScene)
-    DevPrim* d_fprims = nullptr;
-    pbrt_light_desc* d_lights = nullptr;
-    pbrt_camera_desc* d_camera = nullptr;
-    pbrt_film_desc* d_film = nullptr;
-    pbrt_distribution_desc* d_dist = nullptr;
+    DevBuf<DevPrim> d_fprims;
+    DevBuf<pbrt_light_desc> d_lights;
+    DevBuf<pbrt_camera_desc> d_camera;
+    DevBuf<pbrt_film_desc> d_film;
+    DevBuf<pbrt_distribution_desc> d_dist;
     pbrt_scene_desc host_scene;   // counts + film/camera (pointer fields are not kept)
     std::vector<pbrt_light_desc> host_lights;
     bool non_matte = false;       // Mirror, Glass or OrenNayar material: kX wave kernels or the serial kernel
     bool rough_glass = false;     // a Glass material with roughness: serial kernel only
     // per-render buffers (grown on demand)
-    double* d_films = nullptr;
-    size_t films_cap = 0;
-    double* d_s1d = nullptr;
-    size_t s1d_cap = 0;
-    PanicRec* d_panics = nullptr;
-    size_t panics_cap = 0;
-    Counters* d_ctr = nullptr;
-    // k_chain_ci heaviest-first schedule: per-slot chain time of the last
-    // EXACT frame (wall_clock64 ticks) and the slot order derived from it
-    uint32_t* d_ticks = nullptr;         // [kTickPlanes][slots]
-    std::vector<uint32_t> h_tick_clocks; // diagnostics builds: [start | end] clocks of the last frame
-    uint32_t* d_slot_order = nullptr;
-    size_t ticks_cap = 0, order_cap = 0;
-    std::vector<uint32_t> h_slot_order;
+    DevBuf<double> d_films;
+    DevBuf<double> d_s1d;
+    DevBuf<PanicRec> d_panics;
+    DevBuf<Counters> d_ctr;
     // path wavefront (k_pw_*, PBRT_PATHS_WF=1): path records, queues, counters,
     // bounce-1 light estimates, per-pixel panic keys (grown on demand)
-    unsigned char* d_pw = nullptr;
-    size_t pw_cap = 0;
-    // cold-frame schedule (k_tile_cost): per-slot features and sort keys
-    float* d_cost = nullptr;
-    uint64_t* d_cost_keys = nullptr;
-    size_t cost_cap = 0, cost_keys_cap = 0;
-    int64_t cost_n = 0;
-    bool probed = false;               // the last EXACT frame ran the cost probe
-    uint64_t order_key = 0, ticks_key = 0;
-    uint64_t scene_hash = 0;           // content hash of the scene (process-wide schedule cache)
-    int sched_src = 0;                 // schedule of the last EXACT frame: PBRT_SCHED_* (pbrt_diag.h)
-    int64_t ticks_n = 0;
-    bool ticks_pending = false;
-    double* d_out = nullptr;
-    size_t out_cap = 0;
+    DevBuf<unsigned char> d_pw;
+    DevBuf<double> d_out;
     // last render
     RenderParams rp{};
     bool rendered = false;
@@ -268,17 +230,29 @@ struct pbrt_gpu_ctx {
     // kernels poll; it belongs to the render in flight (render_async entry to
     // synchronize) and is cleared when that render ends, so a cancel never
     // outlives its render and never reaches the next one
-    std::mutex cancel_mu;
-    bool in_flight = false;
-    bool cancel_req = false;
-    int* h_cancel = nullptr;   // hipHostMalloc (coherent, mapped)
-    int* d_cancel = nullptr;   // its device address
-    int* d_cancel_seen = nullptr;   // device-memory copy the kernels publish (reset per render)
+    struct {
+        std::mutex mu;
+        bool in_flight = false;
+        bool req = false;
+        int* h_flag = nullptr;   // hipHostMalloc (coherent, mapped)
+        int* d_flag = nullptr;   // its device address
+        DevBuf<int> d_seen;      // device-memory copy the kernels publish (reset per render)
+        // A render begins (in_flight_now) or has ended: the flag is cleared either
+        // way. Returns whether the render that was in flight had been cancelled.
+        bool reset(bool in_flight_now) {
+            std::lock_guard<std::mutex> lk(mu);
+            const bool cancelled = in_flight && req;
+            in_flight = in_flight_now;
+            req = false;
+            __atomic_store_n(h_flag, 0, __ATOMIC_SEQ_CST);
+            return cancelled;
+        }
+    } cancel;
     // device-resident queries: the buffers the context owns (pbrt_gpu_buffer;
     // whatever is left is freed by pbrt_gpu_destroy) and the panic record of
     // the queries since the last pbrt_gpu_query_status (allocated by the first)
     pbrtq::BufferList qbufs;
-    QueryRec* d_qrec = nullptr;
+    DevBuf<QueryRec> d_qrec;
     // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
     // (cleared by render_enqueue) and those outside a frame (LBVH build, queries)
     LaunchLog log_frame, log_aux;
@@ -289,81 +263,16 @@ struct pbrt_gpu_ctx {
 
 namespace {
 
-// Process-wide schedule cache. internal/render/server.go:29-164 builds a fresh
-// scene, integrator and renderer for every request, so each request's context
-// would otherwise start from the cold-frame probe. A context that measured a
-// frame stores its heaviest-first slot order here, keyed by the scene's content
-// hash and the frame's schedule key; a fresh context on the same scene and
-// configuration starts from it. Only the schedule changes, never a result, so a
-// hash collision could only cost speed.
-struct SchedEntry {
-    std::vector<uint32_t> order;   // slot order, heaviest first
-    int64_t heavy_k = 0;           // slots at its front that run at 4 waves
-};
-std::mutex g_sched_mu;
-std::unordered_map<uint64_t, SchedEntry> g_sched;
-constexpr size_t kSchedCacheMax = 64;   // configurations kept (a full frame's order is 32 KB)
-
-uint64_t fnv_bytes(uint64_t h, const void* p, size_t n) {
-    const unsigned char* b = (const unsigned char*)p;
-    for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ull;
-    return h;
-}
-// Content hash of a scene descriptor: every analytic record, the camera and
-// film, and per mesh its sizes plus up to 4096 evenly spread vertices and
-// triangles (a mesh of 10M triangles is not hashed whole on every create).
-uint64_t scene_content_hash(const pbrt_scene_desc* s) {
-    uint64_t h = 1469598103934665603ull;
-    const int32_t counts[] = {s->n_shapes, s->n_materials, s->n_prims, s->n_nodes, s->n_lights, s->n_meshes};
-    h = fnv_bytes(h, counts, sizeof(counts));
-    if (s->n_shapes > 0) h = fnv_bytes(h, s->shapes, sizeof(pbrt_shape_desc) * (size_t)s->n_shapes);
-    if (s->n_materials > 0) h = fnv_bytes(h, s->materials, sizeof(pbrt_material_desc) * (size_t)s->n_materials);
-    if (s->n_prims > 0) h = fnv_bytes(h, s->prims, sizeof(pbrt_primitive_desc) * (size_t)s->n_prims);
-    if (s->n_nodes > 0) h = fnv_bytes(h, s->nodes, sizeof(pbrt_bvh_node) * (size_t)s->n_nodes);
-    if (s->n_lights > 0) h = fnv_bytes(h, s->lights, sizeof(pbrt_light_desc) * (size_t)s->n_lights);
-    h = fnv_bytes(h, &s->camera, sizeof(s->camera));
-    h = fnv_bytes(h, &s->film, sizeof(s->film));
-    for (int m = 0; m < s->n_meshes && s->meshes; m++) {
-        const pbrt_mesh_desc& md = s->meshes[m];
-        const int32_t mc[] = {md.n_vertices, md.n_triangles, md.material, md.reverse_orientation};
-        h = fnv_bytes(h, mc, sizeof(mc));
-        const int64_t nv = md.n_vertices, nt = md.n_triangles;
-        for (int64_t i = 0, st = std::max<int64_t>(1, nv / 4096); md.p && i < nv; i += st)
-            h = fnv_bytes(h, md.p + 3 * i, 3 * sizeof(float));
-        for (int64_t i = 0, st = std::max<int64_t>(1, nt / 4096); md.indices && i < nt; i += st)
-            h = fnv_bytes(h, md.indices + 3 * i, 3 * sizeof(int32_t));
-    }
-    return h;
-}
+// the process cache's key (schedule.h) of a schedule key on this context's scene and device
 uint64_t sched_cache_key(const pbrt_gpu_ctx* c, uint64_t skey) {
     uint64_t h = fnv_bytes(c->scene_hash, &skey, sizeof(skey));
-    return fnv_bytes(h, &c->n_simd, sizeof(c->n_simd));   // the device's size shapes the split
-}
-bool sched_cache_get(const pbrt_gpu_ctx* c, uint64_t skey, int64_t nb, SchedEntry& out) {
-    std::lock_guard<std::mutex> lk(g_sched_mu);
-    auto it = g_sched.find(sched_cache_key(c, skey));
-    if (it == g_sched.end() || (int64_t)it->second.order.size() != nb) return false;
-    out = it->second;
-    return true;
-}
-void sched_cache_put(const pbrt_gpu_ctx* c, uint64_t skey, const std::vector<uint32_t>& order, int64_t heavy_k) {
-    std::lock_guard<std::mutex> lk(g_sched_mu);
-    if (g_sched.size() >= kSchedCacheMax && !g_sched.count(sched_cache_key(c, skey))) g_sched.clear();
-    SchedEntry& e = g_sched[sched_cache_key(c, skey)];
-    e.order = order;
-    e.heavy_k = heavy_k;
+    return fnv_bytes(h, &c->dev.n_simd, sizeof(c->dev.n_simd));   // the device's size shapes the split
 }
 
 int set_err(pbrt_gpu_ctx* c, int code, const std::string& m) {
     if (c) c->err = m;
     return code;
 }
-#define HIPCHK(ctx, call)                                                                            \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return set_err(ctx, PBRT_E_HIP, std::string(#call ": ") + hipGetErrorString(e_));      \
-    } while (0)
 
 // Every launch of a context: the record (launch_log.h), then hipLaunchKernelGGL.
 template <class... P, class... A>
@@ -372,36 +281,18 @@ void launch_k(pbrt_gpu_ctx* c, void (*kern)(P...), dim3 grid, dim3 block, unsign
     launch_logged(c->in_frame ? &c->log_frame : &c->log_aux, sid, kern, grid, block, lds, st, std::forward<A>(args)...);
 }
 
-template <class T>
-int upload(pbrt_gpu_ctx* c, T** dst, const T* src, size_t n) {
-    if (n == 0) n = 1;   // keep a valid pointer for empty arrays
-    HIPCHK(c, hipMalloc((void**)dst, sizeof(T) * n));
-    if (src) HIPCHK(c, hipMemcpy(*dst, src, sizeof(T) * n, hipMemcpyHostToDevice));
-    return PBRT_OK;
-}
-template <class T>
-int ensure(pbrt_gpu_ctx* c, T** buf, size_t* cap, size_t n) {
-    if (*cap >= n && *buf) return PBRT_OK;
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIPCHK(c, hipMalloc((void**)buf, sizeof(T) * (n ? n : 1)));
-    *cap = n;
-    return PBRT_OK;
-}
-
 DevScene dev_scene(const pbrt_gpu_ctx* c, bool with_dist) {
     DevScene s;
-    s.shapes = c->d_shapes;
-    s.materials = c->d_materials;
-    s.prims = c->d_prims;
-    s.nodes = c->d_nodes;
-    s.order = c->d_order;
-    s.fprims = c->d_fprims;
-    s.lights = c->d_lights;
-    s.camera = c->d_camera;
-    s.film = c->d_film;
-    s.dist = with_dist ? c->d_dist : nullptr;
+    s.shapes = c->d_shapes.get();
+    s.materials = c->d_materials.get();
+    s.prims = c->d_prims.get();
+    s.nodes = c->d_nodes.get();
+    s.order = c->d_order.get();
+    s.fprims = c->d_fprims.get();
+    s.lights = c->d_lights.get();
+    s.camera = c->d_camera.get();
+    s.film = c->d_film.get();
+    s.dist = with_dist ? c->d_dist.get() : nullptr;
     s.n_prims = c->host_scene.n_prims;
     s.n_nodes = c->host_scene.n_nodes;
     s.n_lights = c->host_scene.n_lights;
@@ -409,11 +300,11 @@ DevScene dev_scene(const pbrt_gpu_ctx* c, bool with_dist) {
     s.n_leaves = 0;
     for (int i = 0; i < c->host_scene.n_nodes; i++) s.n_leaves += c->h_node_prims[i] > 0;
     s.mesh = c->mesh.view();
-    s.groups = c->d_groups;
-    s.gmasks = c->d_gmasks;
+    s.groups = c->d_groups.get();
+    s.gmasks = c->d_gmasks.get();
     s.n_groups = c->n_groups;
-    s.cancel = c->d_cancel;
-    s.cancel_seen = c->d_cancel_seen;
+    s.cancel = c->cancel.d_flag;
+    s.cancel_seen = c->cancel.d_seen.get();
     // bvh_walk_dense: culling groups over a tree of one primitive per leaf, no meshes
     s.dense_ok = c->knobs.ci_dense && s.n_groups > 0 && s.n_leaves == s.n_prims && s.mesh.n_nodes == 0 &&
                  s.n_nodes <= kLdsNodes;
@@ -444,135 +335,6 @@ std::vector<DevNode> dev_nodes(const pbrt_scene_desc* s) {
     return v;
 }
 
-// Preorder visit tables of the BVH, one per ray-direction octant (bvh_walk,
-// pbrt_path.h). Node i's children: i + 1 and nodes[i].offset; the reference
-// visits offset first when the direction along nodes[i].axis is negative
-// (bvh.go:693-703). depth = far children pending on the reference's stack.
-// Returns false if the node array is not a tree in that depth-first layout.
-bool dev_order(const pbrt_scene_desc* s, std::vector<uint32_t>& out) {
-    const int n = s->n_nodes;
-    out.assign((size_t)16 * (n > 0 ? n : 1), 0u);   // [8][n] preorder, then [8][n] leaves in preorder
-    if (n == 0) return true;
-    struct Item { uint32_t node, depth; int64_t slot; };   // slot: table index whose skip this item sets (-1: none)
-    for (int oct = 0; oct < 8; oct++) {
-        uint32_t* t = out.data() + (size_t)oct * n;
-        std::vector<Item> st;
-        std::vector<int64_t> open;   // table indices of interior nodes whose skip is still unknown
-        int k = 0;
-        st.push_back({0u, 0u, -1});
-        while (!st.empty()) {
-            Item it = st.back();
-            st.pop_back();
-            if (it.slot >= 0) {   // marker: the subtree of table entry `slot` ends here
-                t[it.slot] |= (uint32_t)k << 16;
-                continue;
-            }
-            if (k >= n || it.node >= (uint32_t)n) return false;
-            const pbrt_bvh_node& nd = s->nodes[it.node];
-            const int idx = k++;
-            const bool interior = nd.n_prims == 0;
-            t[idx] = it.node | ((interior && it.depth >= 64) ? kOrdOverflow : 0u);
-            if (!interior) {
-                t[idx] |= (uint32_t)(idx + 1) << 16;
-                continue;
-            }
-            const bool neg = (oct >> nd.axis) & 1;
-            const uint32_t near_node = neg ? nd.offset : it.node + 1, far_node = neg ? it.node + 1 : nd.offset;
-            st.push_back({0u, 0u, (int64_t)idx});            // after both subtrees: set skip
-            st.push_back({far_node, it.depth, -1});           // visited after the near subtree
-            st.push_back({near_node, it.depth + 1, -1});      // far child pending on the stack
-        }
-        if (k != n) return false;
-        int nl = 0;
-        for (int i = 0; i < n; i++) {
-            const uint32_t node = t[i] & kOrdNode;
-            if (s->nodes[node].n_prims > 0) out[(size_t)8 * n + (size_t)oct * n + nl++] = node;
-        }
-    }
-    return true;
-}
-
-// Leaf culling groups of an LDS-staged tree of <= 32 leaves (bvh_walk_analytic): leaves whose
-// box diagonal exceeds half the root's (the README floor and wall disks) and
-// singletons are tested unconditionally; the others are split recursively at
-// the median of their box centres along the widest axis into groups of <= 8
-// (the README's three rows of seven spheres become row segments). A group's
-// box is the exact union of its members' boxes. Output: boxes [G][6], then per
-// octant [G + 1] masks over the octant's leaf preorder positions (last: the
-// unconditional leaves). G = 0 (no culling) when the tree is not LDS-staged
-// or the grouping needs more than kMaxCullGroups groups.
-int cull_groups(const Knobs& kn, const pbrt_scene_desc* s, const std::vector<uint32_t>& order, std::vector<double>& boxes,
-                std::vector<uint32_t>& masks) {
-    boxes.clear();
-    masks.clear();
-    const int n = s->n_nodes;
-    if (n == 0 || n > kLdsNodes) return 0;
-    std::vector<int> leaves;
-    for (int i = 0; i < n; i++)
-        if (s->nodes[i].n_prims > 0) leaves.push_back(i);
-    if (leaves.size() > 32) return 0;
-    auto diag2 = [&](int i) {
-        double d = 0;
-        for (int k = 0; k < 3; k++) d += (s->nodes[i].bmax[k] - s->nodes[i].bmin[k]) * (s->nodes[i].bmax[k] - s->nodes[i].bmin[k]);
-        return d;
-    };
-    const double root = diag2(0);
-    std::vector<int> rest;
-    std::vector<int> group_of((size_t)n, -1);   // -1: unconditional
-    for (int v : leaves)
-        if (!(diag2(v) > 0.25 * root)) rest.push_back(v);
-    std::vector<std::vector<int>> groups;
-    // leaves per group at most: 4 measured best on config B (chain 420 -> 404 ms against 8;
-    // 2: 450, 3: 403, 5: 418, 16: 492; profiles/r02/cull_group_ab.json). PBRT_CULL_GROUP overrides.
-    const size_t gmax = (size_t)kn.cull_group;
-    std::function<void(std::vector<int>)> split = [&](std::vector<int> g) {
-        if (g.size() <= gmax) {
-            if (g.size() > 1) groups.push_back(g);
-            return;
-        }
-        double lo[3] = {kInf, kInf, kInf}, hi[3] = {-kInf, -kInf, -kInf};
-        auto cen = [&](int v, int k) { return 0.5 * (s->nodes[v].bmin[k] + s->nodes[v].bmax[k]); };
-        for (int v : g)
-            for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], cen(v, k)); hi[k] = std::max(hi[k], cen(v, k)); }
-        int a = 0;
-        for (int k = 1; k < 3; k++)
-            if (hi[k] - lo[k] > hi[a] - lo[a]) a = k;
-        std::stable_sort(g.begin(), g.end(), [&](int x, int y) { return cen(x, a) < cen(y, a); });
-        const size_t h = g.size() / 2;
-        split(std::vector<int>(g.begin(), g.begin() + (long)h));
-        split(std::vector<int>(g.begin() + (long)h, g.end()));
-    };
-    if (!rest.empty()) split(rest);
-    const int G = (int)groups.size();
-    // worth it only when the groups can skip a fair share of the leaf tests
-    // (README: 21 of 23 leaves grouped; Cornell: 2 of 8, not grouped)
-    const int min_frac2 = kn.cull_min;   // grouped leaves must be at least half of all (PBRT_CULL_MIN=0: any)
-    if (G == 0 || G > kMaxCullGroups || min_frac2 * (int)rest.size() < (int)leaves.size()) return 0;
-    boxes.assign((size_t)G * 6, 0.0);
-    for (int gi = 0; gi < G; gi++) {
-        for (int k = 0; k < 3; k++) {
-            boxes[(size_t)gi * 6 + k] = kInf;
-            boxes[(size_t)gi * 6 + 3 + k] = -kInf;
-        }
-        for (int v : groups[(size_t)gi]) {
-            group_of[(size_t)v] = gi;
-            for (int k = 0; k < 3; k++) {
-                boxes[(size_t)gi * 6 + k] = std::min(boxes[(size_t)gi * 6 + k], s->nodes[v].bmin[k]);
-                boxes[(size_t)gi * 6 + 3 + k] = std::max(boxes[(size_t)gi * 6 + 3 + k], s->nodes[v].bmax[k]);
-            }
-        }
-    }
-    masks.assign((size_t)8 * (G + 1), 0u);
-    const int nl = (int)leaves.size();
-    for (int oct = 0; oct < 8; oct++)
-        for (int j = 0; j < nl; j++) {
-            const uint32_t node = order[(size_t)8 * n + (size_t)oct * n + (size_t)j];
-            const int gi = group_of[node];
-            masks[(size_t)oct * (G + 1) + (size_t)(gi < 0 ? G : gi)] |= 1u << j;
-        }
-    return G;
-}
-
 std::vector<DevPrim> dev_prims(const pbrt_scene_desc* s) {
     std::vector<DevPrim> v((size_t)(s->n_prims > 0 ? s->n_prims : 1));
     std::memset(v.data(), 0, v.size() * sizeof(DevPrim));
@@ -588,47 +350,6 @@ std::vector<DevPrim> dev_prims(const pbrt_scene_desc* s) {
     return v;
 }
 
-int validate_scene(const pbrt_scene_desc* s) {
-    if (!s) return PBRT_E_INVALID;
-    if (s->n_prims < 0 || s->n_nodes < 0 || s->n_lights < 0 || s->n_shapes < 0 || s->n_materials < 0)
-        return PBRT_E_INVALID;
-    if (s->n_nodes > 32767) return PBRT_E_UNSUPPORTED;   // 15-bit node index in the preorder tables
-    for (int i = 0; i < s->n_prims; i++) {
-        const pbrt_primitive_desc& p = s->prims[i];
-        if (p.shape < 0 || p.shape >= s->n_shapes || p.material < 0 || p.material >= s->n_materials)
-            return PBRT_E_INVALID;
-        if (p.kind != PBRT_PRIM_GEOMETRIC && p.kind != PBRT_PRIM_TRANSFORMED) return PBRT_E_INVALID;
-    }
-    for (int i = 0; i < s->n_shapes; i++)
-        if (s->shapes[i].type != PBRT_SHAPE_SPHERE && s->shapes[i].type != PBRT_SHAPE_DISK) return PBRT_E_UNSUPPORTED;
-    for (int i = 0; i < s->n_nodes; i++) {
-        const pbrt_bvh_node& n = s->nodes[i];
-        if (n.n_prims > 0 && (int64_t)n.offset + n.n_prims > s->n_prims) return PBRT_E_INVALID;
-        if (n.n_prims == 0 && (n.offset >= (uint32_t)s->n_nodes || n.axis > 2)) return PBRT_E_INVALID;
-    }
-    for (int i = 0; i < s->n_materials; i++)
-        if (s->materials[i].type < PBRT_MAT_MATTE || s->materials[i].type > PBRT_MAT_GLASS) return PBRT_E_UNSUPPORTED;
-    if (s->n_meshes < 0 || (s->n_meshes > 0 && !s->meshes)) return PBRT_E_INVALID;
-    for (int i = 0; i < s->n_meshes; i++) {
-        const pbrt_mesh_desc& m = s->meshes[i];
-        if (m.n_vertices < 0 || m.n_triangles < 0 || m.material < 0 || m.material >= s->n_materials ||
-            (m.n_triangles > 0 && (!m.p || !m.indices)))
-            return PBRT_E_INVALID;
-        for (int64_t k = 0; k < 3 * (int64_t)m.n_triangles; k++)
-            if (m.indices[k] < 0 || m.indices[k] >= m.n_vertices) return PBRT_E_INVALID;
-    }
-    for (int i = 0; i < s->n_lights; i++) {
-        const pbrt_light_desc& l = s->lights[i];
-        if (l.type < PBRT_LIGHT_POINT || l.type > PBRT_LIGHT_DIFFUSE_AREA) return PBRT_E_UNSUPPORTED;
-        if (l.type == PBRT_LIGHT_DIFFUSE_AREA &&
-            (l.shape < 0 || l.shape >= s->n_shapes || s->shapes[l.shape].type != PBRT_SHAPE_SPHERE))
-            return PBRT_E_UNSUPPORTED;
-    }
-    const pbrt_film_desc& f = s->film;
-    if (f.crop_max_x <= f.crop_min_x || f.crop_max_y <= f.crop_min_y) return PBRT_E_INVALID;
-    return PBRT_OK;
-}
-
 const PcgJump& pcg_jump_table() {
     static PcgJump J = [] {
         PcgJump t;
@@ -640,6 +361,22 @@ const PcgJump& pcg_jump_table() {
 
 int paths_ci_pixels(const pbrt_gpu_ctx* c, const RenderParams& rp);
 bool paths_wf_enabled(const pbrt_gpu_ctx* c);
+// Offsets into a kernel's dynamic LDS block, handed out in order, each 16-byte aligned.
+struct LdsCarve {
+    int64_t off = 0;
+    int put(int64_t bytes) {
+        const int64_t o = off;
+        off += (bytes + 15) & ~int64_t(15);
+        return (int)o;
+    }
+};
+// A light the distribution never picks (pdf 0) changes the draw count of a light sample.
+bool zero_pdf_light(const pbrt_distribution_desc& d) {
+    if (!(d.func_int > 0)) return true;
+    for (int i = 0; i < d.count; i++)
+        if (!(d.func[i] > 0)) return true;
+    return false;
+}
 // Can the wave-parallel kernels replay this render exactly? (conditions: pbrt_spec.h)
 #ifndef PBRT_SP_SERIAL_KB
 // above this many KB of raw StartPixel draws, StartPixel runs on one lane and
@@ -683,33 +420,23 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
     const int nl = c->host_scene.n_lights;
     // (any light count: beyond the kMaxCachedLights of PixelCache::ld[] paths_ci_pixels answers 0
     // and the path wavefront runs the paths; its k_pw_cache writes global arrays of n_lights per pixel)
-    if (!dl && nl > 0) {
-        const pbrt_distribution_desc& d = c->host_dist;
-        if (!(d.func_int > 0)) return false;
-        for (int i = 0; i < d.count; i++)
-            if (!(d.func[i] > 0)) return false;   // a zero-pdf light changes the draw count
-    }
+    if (!dl && nl > 0 && zero_pdf_light(c->host_dist)) return false;
     // k_film stages the tile film's running sums and a run of source pixels in LDS
     // (any filter radius below the tile size: footprints beyond 2x2 included)
     // (+ its static per-run nvalid array, k_frame.hip)
-    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->lds_per_block) return false;
+    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->dev.lds_per_block) return false;
     const int64_t n = rp.spp, nd = rp.ndims;
     if (n > 4096 || nd * n > 8192) return false;
-    int64_t off = 0;
-    auto put = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 15) & ~int64_t(15);
-        return (int)o;
-    };
-    L.s1d = put(nd * n * 8);
-    L.other = put(nd * n * 2);
-    L.sbuf = put(kWave * 8);
-    L.dbuf = put(kWave * 4);
-    L.vbuf = put(sp_vbuf_bytes(rp));
-    L.total = (int)off;
+    LdsCarve lds;
+    L.s1d = lds.put(nd * n * 8);
+    L.other = lds.put(nd * n * 2);
+    L.sbuf = lds.put(kWave * 8);
+    L.dbuf = lds.put(kWave * 4);
+    L.vbuf = lds.put(sp_vbuf_bytes(rp));
+    L.total = (int)lds.off;
     L.ring = 0;
     // k_chain_ci: the same staging without the window buffers, then the ring
-    off = 0;
+    lds = LdsCarve{};
     // the pixel's stratified values are staged in LDS while the staging of one
     // 1-wave tile (aliased with the ring) stays <= PBRT_CI_STAGE_KB; above,
     // StartPixel writes them straight to the pixel's global record (always with
@@ -721,22 +448,22 @@ bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const Rend
                                 ((sp_vbuf_bytes(rp) + al16) & ~al16);
     if (rp.sp_window) {   // the windowed StartPixel: picks in LDS, values straight to the global record
         Lci.s1d = -1;
-        Lci.other = put(nd * n * 2);
+        Lci.other = lds.put(nd * n * 2);
     } else if (rp.sp_serial) {
         Lci.s1d = -1;
-        Lci.other = put(16);
+        Lci.other = lds.put(16);
     } else if (lds_staging > PBRT_CI_STAGE_KB * 1024) {
         Lci.s1d = -1;
-        Lci.other = put(nd * n * 2);
+        Lci.other = lds.put(nd * n * 2);
     } else {
-        Lci.s1d = put(nd * n * 8);
-        Lci.other = put(nd * n * 2);
+        Lci.s1d = lds.put(nd * n * 8);
+        Lci.other = lds.put(nd * n * 2);
     }
     Lci.sbuf = Lci.dbuf = 0;
-    Lci.vbuf = put(sp_vbuf_bytes(rp));
-    Lci.staging = (int)off;
-    Lci.ring = put(kCiRingBytes);
-    Lci.total = (int)off;
+    Lci.vbuf = lds.put(sp_vbuf_bytes(rp));
+    Lci.staging = (int)lds.off;
+    Lci.ring = lds.put(kCiRingBytes);
+    Lci.total = (int)lds.off;
     return L.total <= 48 * 1024;
 }
 
@@ -763,30 +490,20 @@ bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const 
     if (c->non_matte) return no("Mirror / Glass / OrenNayar materials");
     if (c->mesh.n_nodes != 0) return no("triangle meshes");
     const int nl = c->host_scene.n_lights;
-    if (nl > 0) {
-        const pbrt_distribution_desc& d = c->host_dist;
-        if (!(d.func_int > 0)) return no("a light with pdf 0");
-        for (int i = 0; i < d.count; i++)
-            if (!(d.func[i] > 0)) return no("a light with pdf 0");   // it changes the draw count
-    }
-    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->lds_per_block)
+    if (nl > 0 && zero_pdf_light(c->host_dist)) return no("a light with pdf 0");
+    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->dev.lds_per_block)
         return no("the tile film does not fit LDS");
     const int64_t n = rp.spp, nd = rp.ndims;
     if (n > 4096 || nd * n > 8192) return no("more than 4096 samples per pixel");
-    int64_t off = 0;
-    auto put = [&](int64_t bytes) {
-        int64_t o = off;
-        off += (bytes + 15) & ~int64_t(15);
-        return (int)o;
-    };
+    LdsCarve lds;
     L = ChainLayout{};
     // (large spp: the serial StartPixel writes straight to the pixel's global record)
-    L.s1d = rp.sp_serial || nd == 0 ? -1 : put(nd * n * 8);
-    L.other = put(rp.sp_serial ? 16 : nd * n * 2 + 16);
-    L.vbuf = put(rp.sp_serial ? 4 : sp_vbuf_bytes(rp));
-    L.staging = (int)off;
+    L.s1d = rp.sp_serial || nd == 0 ? -1 : lds.put(nd * n * 8);
+    L.other = lds.put(rp.sp_serial ? 16 : nd * n * 2 + 16);
+    L.vbuf = lds.put(rp.sp_serial ? 4 : sp_vbuf_bytes(rp));
+    L.staging = (int)lds.off;
     L.ring = 0;
-    L.total = std::max((int)off, kCiRingBytes);
+    L.total = std::max((int)lds.off, kCiRingBytes);
     return true;
 }
 
@@ -915,7 +632,7 @@ int ci_waves(const pbrt_gpu_ctx* c, int64_t nb) {
     if (c->tiles_per_wave > 1) return 1;
     // measured on config B shards (tools/shard_sim.py): 8160 tiles -> 1,
     // 4080 -> 2, 2040 and 1020 -> 4
-    const int64_t slots = (int64_t)c->n_simd * 2;   // 2 waves/SIMD
+    const int64_t slots = (int64_t)c->dev.n_simd * 2;   // 2 waves/SIMD
     if (nb <= slots) return 4;
     if (nb <= 2 * slots) return 2;
     return 1;
@@ -942,7 +659,7 @@ bool ci_eu3_fits(const pbrt_gpu_ctx* c, unsigned dyn_lds, bool lds_nodes, bool m
     size_t stat = 0;
     if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat = fa.sharedSizeBytes;
     const size_t per_wg = stat + dyn_lds;
-    return per_wg > 0 && c->lds_per_cu / per_wg >= 12;
+    return per_wg > 0 && c->dev.lds_per_cu / per_wg >= 12;
 }
 int64_t ci_heavy_override(const pbrt_gpu_ctx* c) { return c->knobs.ci_heavy; }
 // k_chain_ci candidate stride: 2 issues candidates at the chain head's parity
@@ -1032,8 +749,8 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
     const size_t need = (size_t)(al(cap * (int64_t)sizeof(PwPath)) + 4 * al(cap * 4) + al(ncnt * 4) +
                                  al(chunk * std::max(nl, 1) * (int64_t)sizeof(Spec)) + al(chunk * std::max(nl, 1) * 4) +
                                  al(nrec * 8));
-    if (const int rc = ensure(c, &c->d_pw, &c->pw_cap, need)) return rc;
-    unsigned char* p = c->d_pw;
+    if (const int rc = c->d_pw.ensure(c, need)) return rc;
+    unsigned char* p = c->d_pw.get();
     auto take = [&](int64_t bytes) {
         unsigned char* q = p;
         p += al(bytes);
@@ -1048,7 +765,7 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
     Spec* ldc = (Spec*)take(chunk * std::max(nl, 1) * (int64_t)sizeof(Spec));
     int* ldp = (int*)take(chunk * std::max(nl, 1) * 4);
     unsigned long long* pkey = (unsigned long long*)take(nrec * 8);
-    const unsigned G = (unsigned)std::max<int64_t>(64, (int64_t)c->n_simd * 8);   // grid-stride blocks
+    const unsigned G = (unsigned)std::max<int64_t>(64, (int64_t)c->dev.n_simd * 8);   // grid-stride blocks
     HIPCHK(c, hipMemsetAsync(pkey, 0xFF, (size_t)nrec * 8, c->stream));
     const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
     const bool kx = c->non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
@@ -1078,7 +795,7 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
             }
         }
         launch_k(c, k_pw_panics, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, sb, r0,
-                           nr, pkey, c->d_ctr);
+                           nr, pkey, c->d_ctr.get());
     }
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
@@ -1102,16 +819,16 @@ int wave_buffers(pbrt_gpu_ctx* c) {
     {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-            gb = std::min(gb, 0.5 * (double)(free_b + c->wave_cap) / 1073741824.0);
+            gb = std::min(gb, 0.5 * (double)(free_b + c->d_wave.cap()) / 1073741824.0);
     }
     if (c->knobs.wave_buffer_gb > 0) gb = c->knobs.wave_buffer_gb;
     int64_t batch = (int64_t)(gb * 1073741824.0) / per_tile;
     if (batch < 1) batch = 1;
     if (batch > rp.n_slots) batch = rp.n_slots > 0 ? rp.n_slots : 1;
     const size_t need = (size_t)(batch * per_tile);
-    if (const int rc = ensure(c, &c->d_wave, &c->wave_cap, need)) return rc;
+    if (const int rc = c->d_wave.ensure(c, need)) return rc;
     WaveBufs& wb = c->wb;
-    unsigned char* p = c->d_wave;
+    unsigned char* p = c->d_wave.get();
     auto take = [&](int64_t bytes_per_tile) {
         unsigned char* q = p;
         p += batch * al(bytes_per_tile);
@@ -1188,7 +905,7 @@ int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
     if (rd->integrator == PBRT_INTEGRATOR_PATH) {
         int rc = pbrt_scene_light_distribution(&c->host_scene, rd->light_strategy, &dist);
         if (rc != PBRT_OK) return set_err(c, rc, "unsupported light sample strategy");
-        HIPCHK(c, hipMemcpyAsync(c->d_dist, &dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_dist.get(), &dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
     }
     {
         const int64_t n = rp.spp, s1 = rp.jitter ? 2 * n : n, s2 = rp.jitter ? 3 * n : n;
@@ -1245,11 +962,11 @@ int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
     }
     size_t nslot = (size_t)(rp.n_slots > 0 ? rp.n_slots : 1);
     int rc;
-    if ((rc = ensure(c, &c->d_films, &c->films_cap, nslot * (size_t)(rp.slot_w * rp.slot_h * 3)))) return rc;
-    if ((rc = ensure(c, &c->d_s1d, &c->s1d_cap, nslot * (size_t)(rp.ndims > 0 ? rp.ndims : 1) * (size_t)rp.spp)))
+    if ((rc = c->d_films.ensure(c, nslot * (size_t)(rp.slot_w * rp.slot_h * 3)))) return rc;
+    if ((rc = c->d_s1d.ensure(c, nslot * (size_t)(rp.ndims > 0 ? rp.ndims : 1) * (size_t)rp.spp)))
         return rc;
-    if ((rc = ensure(c, &c->d_panics, &c->panics_cap, nslot))) return rc;
-    if ((rc = ensure(c, &c->d_out, &c->out_cap, (size_t)(rp.film_w * rp.film_h * 3)))) return rc;
+    if ((rc = c->d_panics.ensure(c, nslot))) return rc;
+    if ((rc = c->d_out.ensure(c, (size_t)(rp.film_w * rp.film_h * 3)))) return rc;
     return PBRT_OK;
 }
 
@@ -1289,9 +1006,9 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) {
-            c->n_simd = 4 * prop.multiProcessorCount;
-            c->lds_per_block = prop.sharedMemPerBlock;
-            if (prop.maxSharedMemoryPerMultiProcessor > 0) c->lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
+            c->dev.n_simd = 4 * prop.multiProcessorCount;
+            c->dev.lds_per_block = prop.sharedMemPerBlock;
+            if (prop.maxSharedMemoryPerMultiProcessor > 0) c->dev.lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
         }
     }
     std::vector<uint32_t> order;
@@ -1327,33 +1044,33 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
         return PBRT_E_HIP;
     }
 
-    if (hipHostMalloc((void**)&c->h_cancel, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->d_cancel, c->h_cancel, 0) != hipSuccess) {
+    if (hipHostMalloc((void**)&c->cancel.h_flag, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer((void**)&c->cancel.d_flag, c->cancel.h_flag, 0) != hipSuccess) {
         pbrt_gpu_destroy(c);
         return PBRT_E_HIP;
     }
-    __atomic_store_n(c->h_cancel, 0, __ATOMIC_SEQ_CST);
-    if ((rc = upload(c, &c->d_shapes, scene->shapes, scene->n_shapes)) ||
-        (rc = upload(c, &c->d_materials, scene->materials, scene->n_materials)) ||
-        (rc = upload(c, &c->d_prims, scene->prims, scene->n_prims)) ||
-        (rc = upload(c, &c->d_nodes, dev_nodes(scene).data(), scene->n_nodes)) ||
-        (rc = upload(c, &c->d_order, order.data(), order.size())) ||
-        (rc = upload(c, &c->d_fprims, dev_prims(scene).data(), scene->n_prims)) ||
-        (rc = upload(c, &c->d_lights, scene->lights, scene->n_lights)) ||
-        (rc = upload(c, &c->d_camera, &scene->camera, 1)) || (rc = upload(c, &c->d_film, &scene->film, 1)) ||
-        (rc = upload<pbrt_distribution_desc>(c, &c->d_dist, nullptr, 1)) ||
-        (rc = upload<Counters>(c, &c->d_ctr, nullptr, 1)) || (rc = upload<int>(c, &c->d_cancel_seen, nullptr, 1)) ||
-        (rc = upload<PcgJump>(c, &c->d_jump, &pcg_jump_table(), 1))) {
+    __atomic_store_n(c->cancel.h_flag, 0, __ATOMIC_SEQ_CST);
+    if ((rc = c->d_shapes.upload(c, scene->shapes, scene->n_shapes)) ||
+        (rc = c->d_materials.upload(c, scene->materials, scene->n_materials)) ||
+        (rc = c->d_prims.upload(c, scene->prims, scene->n_prims)) ||
+        (rc = c->d_nodes.upload(c, dev_nodes(scene).data(), scene->n_nodes)) ||
+        (rc = c->d_order.upload(c, order.data(), order.size())) ||
+        (rc = c->d_fprims.upload(c, dev_prims(scene).data(), scene->n_prims)) ||
+        (rc = c->d_lights.upload(c, scene->lights, scene->n_lights)) ||
+        (rc = c->d_camera.upload(c, &scene->camera, 1)) || (rc = c->d_film.upload(c, &scene->film, 1)) ||
+        (rc = c->d_dist.upload(c, nullptr, 1)) ||
+        (rc = c->d_ctr.upload(c, nullptr, 1)) || (rc = c->cancel.d_seen.upload(c, nullptr, 1)) ||
+        (rc = c->d_jump.upload(c, &pcg_jump_table(), 1))) {
         pbrt_gpu_destroy(c);
         return rc;
     }
     {   // leaf culling groups of the LDS-staged walk
         std::vector<double> gb;
         std::vector<uint32_t> gm;
-        c->n_groups = cull_groups(c->knobs, scene, order, gb, gm);
+        c->n_groups = cull_groups(c->knobs.cull_group, c->knobs.cull_min, scene, order, gb, gm);
         if (!c->knobs.cull_groups) c->n_groups = 0;   // PBRT_CULL_GROUPS=0: test every leaf (A/B)
-        if (c->n_groups > 0 && ((rc = upload(c, &c->d_groups, gb.data(), gb.size())) ||
-                                (rc = upload(c, &c->d_gmasks, gm.data(), gm.size())))) {
+        if (c->n_groups > 0 && ((rc = c->d_groups.upload(c, gb.data(), gb.size())) ||
+                                (rc = c->d_gmasks.upload(c, gm.data(), gm.size())))) {
             pbrt_gpu_destroy(c);
             return rc;
         }
@@ -1377,22 +1094,13 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
 
 int pbrt_gpu_render_async_into(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_device) {
     if (!c) return PBRT_E_INVALID;
-    {   // from here on this render is the one pbrt_gpu_cancel cancels: a cancel
-        // that lands while prepare() sizes and allocates the buffers is kept
-        std::lock_guard<std::mutex> lk(c->cancel_mu);
-        c->in_flight = true;
-        c->cancel_req = false;
-        __atomic_store_n(c->h_cancel, 0, __ATOMIC_SEQ_CST);
-    }
-    if (rd) c->last_rd = *rd;   // kept for a re-render (pbrt_gpu_synchronize)
-    c->last_film_device = film_device;
+    // from here on this render is the one pbrt_gpu_cancel cancels: a cancel
+    // that lands while prepare() sizes and allocates the buffers is kept
+    c->cancel.reset(true);
+    if (rd) c->ov.last_rd = *rd;   // kept for a re-render (pbrt_gpu_synchronize)
+    c->ov.last_film_device = film_device;
     const int rc = render_enqueue(c, rd, film_device);
-    if (rc != PBRT_OK) {   // nothing was launched (or the launch failed): no render is in flight
-        std::lock_guard<std::mutex> lk(c->cancel_mu);
-        c->in_flight = false;
-        c->cancel_req = false;
-        __atomic_store_n(c->h_cancel, 0, __ATOMIC_SEQ_CST);
-    }
+    if (rc != PBRT_OK) c->cancel.reset(false);   // nothing was launched (or the launch failed): no render is in flight
     return rc;
 }
 
@@ -1436,29 +1144,29 @@ int ensure_batch_events(pbrt_gpu_ctx* c) {
 // cache_heavy_k its heavy count too), uploads it, and arms pbrt_gpu_synchronize's tick readback.
 int chain_schedule(pbrt_gpu_ctx* c, uint64_t key, int64_t nb, bool cache_heavy_k, Schedule& s) {
     int rc;
-    if ((rc = ensure(c, &c->d_ticks, &c->ticks_cap, (size_t)nb * kTickPlanes)) ||
-        (rc = ensure(c, &c->d_slot_order, &c->order_cap, (size_t)nb)))
+    if ((rc = c->sched.d_ticks.ensure(c, (size_t)nb * kTickPlanes)) ||
+        (rc = c->sched.d_slot_order.ensure(c, (size_t)nb)))
         return rc;
-    auto known = [&] { return c->order_key == key && (int64_t)c->h_slot_order.size() == nb; };
+    auto known = [&] { return c->sched.order_key == key && (int64_t)c->sched.h_slot_order.size() == nb; };
     bool cached = false;
     SchedEntry e;
-    if (!known() && ci_order_cache(c) && sched_cache_get(c, key, nb, e)) {
-        c->h_slot_order = std::move(e.order);
-        if (cache_heavy_k) c->heavy_k = e.heavy_k;
-        c->order_key = key;
+    if (!known() && ci_order_cache(c) && sched_cache_get(sched_cache_key(c, key), nb, e)) {
+        c->sched.h_slot_order = std::move(e.order);
+        if (cache_heavy_k) c->sched.heavy_k = e.heavy_k;
+        c->sched.order_key = key;
         cached = true;
     }
     if (known()) {
-        c->sched_src = cached ? PBRT_SCHED_CACHED : PBRT_SCHED_LEARNED;
-        HIPCHK(c, hipMemcpyAsync(c->d_slot_order, c->h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
+        c->sched.src = cached ? PBRT_SCHED_CACHED : PBRT_SCHED_LEARNED;
+        HIPCHK(c, hipMemcpyAsync(c->sched.d_slot_order.get(), c->sched.h_slot_order.data(), sizeof(uint32_t) * (size_t)nb,
                                  hipMemcpyHostToDevice, c->stream));
-        s.order = c->d_slot_order;
+        s.order = c->sched.d_slot_order.get();
         s.learned = true;
     }
-    s.ticks = c->d_ticks;
-    c->ticks_pending = true;
-    c->ticks_key = key;
-    c->ticks_n = nb;
+    s.ticks = c->sched.d_ticks.get();
+    c->sched.ticks_pending = true;
+    c->sched.ticks_key = key;
+    c->sched.ticks_n = nb;
     return PBRT_OK;
 }
 
@@ -1468,18 +1176,18 @@ int probe_order(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
     int64_t npad = 2048;
     while (npad < b.nb) npad <<= 1;
     int rc;
-    if ((rc = ensure(c, &c->d_cost, &c->cost_cap, 4 * (size_t)npad)) ||
-        (rc = ensure(c, &c->d_cost_keys, &c->cost_keys_cap, (size_t)npad)))
+    if ((rc = c->sched.d_cost.ensure(c, 4 * (size_t)npad)) ||
+        (rc = c->sched.d_cost_keys.ensure(c, (size_t)npad)))
         return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_cost_keys, 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->sched.d_cost_keys.get(), 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
     launch_k(c, c->non_matte ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)b.nb), dim3(kWave), 0, c->stream,
-             with_slot(sc, 0), c->rp, c->wb, b.sb, b.nb, c->d_cost, c->d_cost_keys);
-    bitonic_sort_u64(c->d_cost_keys, (uint32_t)npad, c->stream, &c->log_frame);
-    launch_k(c, k_order_of_keys, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->d_cost_keys, b.nb,
-             c->d_slot_order);
-    c->probed = true;
-    c->sched_src = PBRT_SCHED_PROBE;
-    c->cost_n = b.nb;
+             with_slot(sc, 0), c->rp, c->wb, b.sb, b.nb, c->sched.d_cost.get(), c->sched.d_cost_keys.get());
+    bitonic_sort_u64(c->sched.d_cost_keys.get(), (uint32_t)npad, c->stream, &c->log_frame);
+    launch_k(c, k_order_of_keys, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->sched.d_cost_keys.get(), b.nb,
+             c->sched.d_slot_order.get());
+    c->sched.probed = true;
+    c->sched.src = PBRT_SCHED_PROBE;
+    c->sched.cost_n = b.nb;
     return PBRT_OK;
 }
 
@@ -1489,13 +1197,13 @@ void launch_films(pbrt_gpu_ctx* c, const Batch& b) {
     const RenderParams& rp = c->rp;
     if (c->use_cam && rp.ndims == 0)
         launch_k(c, rp.mode == PBRT_MODE_THROUGHPUT ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)b.nb),
-                 dim3(kFilmThreads), 0, c->stream, c->d_film, rp, c->wb, b.sb, b.nb, c->d_films, c->d_cancel_seen,
-                 c->d_ctr);
+                 dim3(kFilmThreads), 0, c->stream, c->d_film.get(), rp, c->wb, b.sb, b.nb, c->d_films.get(), c->cancel.d_seen.get(),
+                 c->d_ctr.get());
     else
         launch_k(c, k_film, dim3((unsigned)b.nb), dim3(kFilmThreads), (unsigned)film_lds_bytes(rp), c->stream,
-                 c->d_film, rp, c->wb, b.sb, b.nb, c->d_films, c->d_cancel_seen, c->d_ctr);
+                 c->d_film.get(), rp, c->wb, b.sb, b.nb, c->d_films.get(), c->cancel.d_seen.get(), c->d_ctr.get());
     launch_k(c, k_panic_reduce, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->wb, b.sb, b.nb,
-             c->d_panics, c->d_ctr);
+             c->d_panics.get(), c->d_ctr.get());
 }
 
 // The camera-start route (PBRT_KERNEL_WAVE_CAM), per batch on the one stream:
@@ -1511,8 +1219,8 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
     c->last_kernel = PBRT_KERNEL_WAVE_CAM;
     int rc = ensure_batch_events(c);
     if (rc != PBRT_OK) return rc;
-    c->ov_done = 0;
-    c->probed = false;   // this route never probes
+    c->ov.done = 0;
+    c->sched.probed = false;   // this route never probes
     for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
         Batch b{bi, sb, std::min<int64_t>(c->wave_batch, rp.n_slots - sb)};
         const int64_t nb = b.nb, nrec = nb * c->wb.ppt;
@@ -1520,19 +1228,19 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
         if (mb) {
             const int64_t blocks = rp.ndims > 0 ? nrec : (nrec + kWave - 1) / kWave;
             launch_k(c, k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
-                     with_slot(sc, 4), rp, c->lay_cam, c->d_jump, c->wb, sb, nb);
+                     with_slot(sc, 4), rp, c->lay_cam, c->d_jump.get(), c->wb, sb, nb);
         } else {
             if (c->n_batches == 1 && ci_order_enabled(c)) {
                 // key -1: no k_chain_ci launch has this wave count. A cached entry's heavy count is the
                 // chain route's: there is no split here, every slot runs 1 wave at 3 waves/SIMD
                 if ((rc = chain_schedule(c, schedule_key(rp, -1), nb, false, b.sched)) != PBRT_OK) return rc;
                 if (kTickPlanes > 1)  // diagnostics builds read start / end clocks this kernel does not record
-                    HIPCHK(c, hipMemsetAsync(c->d_ticks, 0, sizeof(uint32_t) * (size_t)nb * kTickPlanes, c->stream));
-                c->h_slot_kw.assign((size_t)nb, (uint8_t)1);
-                c->ci_wps = 3;
+                    HIPCHK(c, hipMemsetAsync(c->sched.d_ticks.get(), 0, sizeof(uint32_t) * (size_t)nb * kTickPlanes, c->stream));
+                c->sched.h_slot_kw.assign((size_t)nb, (uint8_t)1);
+                c->sched.ci_wps = 3;
             }
             launch_k(c, stack ? k_chain_cam_stack : k_chain_cam, dim3((unsigned)nb), dim3(kWave),
-                     (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump, c->wb, sb, nb,
+                     (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump.get(), c->wb, sb, nb,
                      b.sched.order, b.sched.ticks);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
@@ -1543,7 +1251,7 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
             const PathsCamKernel kern = paths_cam_kernel(pp, mb, stack);
             if (!kern) return set_err(c, PBRT_E_HIP, "no k_paths_cam instantiation for P = " + std::to_string(pp));
             launch_k(c, kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
-                     with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr);
+                     with_slot(sc, mb ? 5 : 3), rp, c->wb, sb, nrec, c->d_ctr.get());
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 2], c->stream));
         launch_films(c, b);
@@ -1561,7 +1269,7 @@ void launch_primary(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
 // THROUGHPUT: k_mb_setup (StartPixel + bounce 1 per pixel) instead of the chain.
 void launch_mb_setup(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
     launch_k(c, c->non_matte ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(b.nb * c->wb.ppt)), dim3(kWave),
-             (unsigned)c->lay.total, c->stream, with_slot(sc, 4), c->rp, c->lay, c->d_jump, c->wb, b.sb, b.nb);
+             (unsigned)c->lay.total, c->stream, with_slot(sc, 4), c->rp, c->lay, c->d_jump.get(), c->wb, b.sb, b.nb);
 }
 
 // k_paths_ci (lane-refill paths) over n slots of the batch on stream st; ord: the slots' order,
@@ -1579,7 +1287,7 @@ int launch_paths(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, bool mb, c
     // ordered: whole slots, ceil(ppt / pp) workgroups each (pp need not divide ppt)
     const int64_t groups = ord ? n * ((c->wb.ppt + pp - 1) / pp) : (n * c->wb.ppt + pp - 1) / pp;
     launch_k(c, kern, dim3((unsigned)groups), dim3(kWave), (unsigned)lds, st, with_slot(sc, mb ? 5 : 3), rp, c->wb,
-             b.sb, n * c->wb.ppt, c->d_ctr, sl, ord);
+             b.sb, n * c->wb.ppt, c->d_ctr.get(), sl, ord);
     return PBRT_OK;
 }
 
@@ -1589,7 +1297,7 @@ int launch_paths(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, bool mb, c
 // which only launches of multi-wave tiles use. The heavy launch of a split does without it unless
 // its light tiles are multi-wave too: its two rings' LDS cost the light tiles beside it (1/4 shard
 // of B 132 -> 145 ms; a 1/8 shard, no split: 131.5 -> 127.2 ms).
-// Sets c->ci_wps for a one-wave launch (pbrt_gpu_synchronize's heavy threshold reads it).
+// Sets c->sched.ci_wps for a one-wave launch (pbrt_gpu_synchronize's heavy threshold reads it).
 int launch_ci(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int w, int64_t n, const uint32_t* ord,
               hipStream_t st, uint32_t* prog, bool nps_allowed) {
     const bool kx = c->non_matte, mesh_only = mesh_only_scene(c), lds_nodes = tree_in_lds(c);
@@ -1609,7 +1317,7 @@ int launch_ci(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int w, int64_
         const bool eu2 = !kx && !mesh_only &&
                          (c->knobs.ci_eu == 2 || (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes, Gc > 1)));
         eu = eu2 ? 2 : 0;
-        c->ci_wps = (kx || eu2) ? 2 : 3;
+        c->sched.ci_wps = (kx || eu2) ? 2 : 3;
     }
     // The instantiation, stated once. Walk: a mesh-only scene has no analytic one (-1), else the
     // staged tree (0) or the [64] stack (64). rp.sp_window is set for Matte scenes of staged trees
@@ -1627,7 +1335,7 @@ int launch_ci(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int w, int64_
     const int ring = w * kCiRingBytes / (int)sizeof(RingEnt) / Gc;
     const bool per_tile = Gc == 1;   // the order and the clocks need one tile per workgroup
     launch_k(c, kern, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
-             c->d_jump, c->wb, b.sb, b.nb, kWave * w / Gc, ring, c->d_ctr, per_tile ? ord : nullptr,
+             c->d_jump.get(), c->wb, b.sb, b.nb, kWave * w / Gc, ring, c->d_ctr.get(), per_tile ? ord : nullptr,
              per_tile ? b.sched.ticks : nullptr, ci_stride(c, w), prog);
     return PBRT_OK;
 }
@@ -1661,15 +1369,15 @@ Split ci_split(const pbrt_gpu_ctx* c, int64_t nb, int kw, bool learned, int G, b
         (void)ci_layout(c->lay_ci, 1, 1, lds1);
         split1 = ci_eu3_fits(c, lds1, tree_in_lds(c));
     }
-    if (learned && G == 1 && (kw > 1 ? nb > c->n_simd : split1) && ci_split_enabled(c))
-        s.heavy = std::min<int64_t>(c->heavy_k, nb);
+    if (learned && G == 1 && (kw > 1 ? nb > c->dev.n_simd : split1) && ci_split_enabled(c))
+        s.heavy = std::min<int64_t>(c->sched.heavy_k, nb);
     if (ci_heavy_override(c) >= 0 && learned && G == 1)   // tests and experiments force the split
         s.heavy = std::min<int64_t>(ci_heavy_override(c), nb);
     // a multi-wave Matte shard that fits the wave slots (1/8 of B: 1020 tiles at 4 waves)
     // is bound by its heaviest tiles' pixel-serial chains: those at 8 waves, the
     // rest at kw, next-pixel speculation in both (the N=8 shards' max 121.9 ->
     // ~107 ms with 32; 4-32 within a few ms; all tiles at 8 waves: 178 ms)
-    if (s.heavy == 0 && ci_heavy_override(c) < 0 && learned && G == 1 && kw > 1 && nb <= c->n_simd && !kx &&
+    if (s.heavy == 0 && ci_heavy_override(c) < 0 && learned && G == 1 && kw > 1 && nb <= c->dev.n_simd && !kx &&
         !mesh_only && ci_split_enabled(c) && c->knobs.ci_split8 > 0) {
         s.heavy = std::min<int64_t>(c->knobs.ci_split8, nb / 16);
         s.light_kw = true;
@@ -1696,17 +1404,17 @@ Split ci_split(const pbrt_gpu_ctx* c, int64_t nb, int kw, bool learned, int G, b
 // overlap_arm: stream3 and its events (created on first use), the progress record (layout at
 // kProgHead) grown and reset, and ev_split on the main stream, which every other stream waits for.
 int overlap_arm(pbrt_gpu_ctx* c, int64_t nb) {
-    if (!c->stream3) {
+    if (!c->ov.stream3) {
         int least = 0, greatest = 0;
         HIPCHK(c, hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(c, hipStreamCreateWithPriority(&c->stream3, hipStreamNonBlocking, greatest));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_l2, hipEventDisableTiming));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_p1, hipEventDisableTiming));
+        HIPCHK(c, hipStreamCreateWithPriority(&c->ov.stream3, hipStreamNonBlocking, greatest));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ov.ev_l2, hipEventDisableTiming));
+        HIPCHK(c, hipEventCreateWithFlags(&c->ov.ev_p1, hipEventDisableTiming));
     }
-    const int rc = ensure(c, &c->d_prog, &c->prog_cap, (size_t)(nb + kProgHead));
+    const int rc = c->ov.d_prog.ensure(c, (size_t)(nb + kProgHead));
     if (rc != PBRT_OK) return rc;
-    HIPCHK(c, hipMemsetAsync(c->d_prog, 0, kProgHead * sizeof(uint32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_prog + kProgHead, 0xFF, sizeof(uint32_t) * (size_t)nb, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ov.d_prog.get(), 0, kProgHead * sizeof(uint32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ov.d_prog.get() + kProgHead, 0xFF, sizeof(uint32_t) * (size_t)nb, c->stream));
     HIPCHK(c, hipEventRecord(c->ev_split, c->stream));
     return PBRT_OK;
 }
@@ -1715,24 +1423,24 @@ int launch_path_chunks(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
     for (int64_t s0 = 0, j = 0; s0 < b.nb; j++) {
         const int64_t e0 = j + 1 >= c->knobs.paths_overlap ? b.nb : s0 + std::max<int64_t>(1, (b.nb - s0) / 2);
-        launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->d_prog, (uint32_t)s0, (uint32_t)e0, c->d_ctr);
-        const int rc = launch_paths(c, sc, b, false, c->d_prog + kProgHead + s0, e0 - s0, c->stream2);
+        launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->ov.d_prog.get(), (uint32_t)s0, (uint32_t)e0, c->d_ctr.get());
+        const int rc = launch_paths(c, sc, b, false, c->ov.d_prog.get() + kProgHead + s0, e0 - s0, c->stream2);
         if (rc != PBRT_OK) return rc;
         s0 = e0;
     }
-    HIPCHK(c, hipEventRecord(c->ev_p1, c->stream2));
+    HIPCHK(c, hipEventRecord(c->ov.ev_p1, c->stream2));
     return PBRT_OK;
 }
 // the light launch of an overlapped split on stream3, behind its k_gate; ev_l2 when it is queued.
 // PBRT_GATE_HOLD: it waits for the whole path stage (ev_p1) instead of ev_split
 int launch_light_gated(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split& sp) {
-    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->knobs.gate_hold ? c->ev_p1 : c->ev_split, 0));
-    launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream3, c->d_prog, (uint32_t)sp.heavy, (uint32_t)sp.heavy,
-             c->d_ctr);
-    const int rc = launch_ci(c, sc, b, sp.light_w, b.nb - sp.heavy, b.sched.order + sp.heavy, c->stream3, c->d_prog, true);
+    HIPCHK(c, hipStreamWaitEvent(c->ov.stream3, c->knobs.gate_hold ? c->ov.ev_p1 : c->ev_split, 0));
+    launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->ov.stream3, c->ov.d_prog.get(), (uint32_t)sp.heavy, (uint32_t)sp.heavy,
+             c->d_ctr.get());
+    const int rc = launch_ci(c, sc, b, sp.light_w, b.nb - sp.heavy, b.sched.order + sp.heavy, c->ov.stream3, c->ov.d_prog.get(), true);
     if (rc != PBRT_OK) return rc;
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
+    HIPCHK(c, hipEventRecord(c->ov.ev_l2, c->ov.stream3));
     return PBRT_OK;
 }
 
@@ -1752,27 +1460,27 @@ int chain_split(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split
 // 3: overlapped split on streams 0, 3 and 2 (after overlap_arm). PBRT_GATE_HOLD queues the path
 // chunks before the light launch.
 int chain_split_overlap(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, const Split& sp) {
-    int rc = launch_ci(c, sc, b, sp.heavy_w, sp.heavy, b.sched.order, c->stream, c->d_prog, sp.light_kw);
+    int rc = launch_ci(c, sc, b, sp.heavy_w, sp.heavy, b.sched.order, c->stream, c->ov.d_prog.get(), sp.light_kw);
     if (rc != PBRT_OK) return rc;
     HIPCHK(c, hipGetLastError());   // the gates below wait for these workgroups
     rc = c->knobs.gate_hold ? launch_path_chunks(c, sc, b) : launch_light_gated(c, sc, b, sp);
     if (rc != PBRT_OK) return rc;
     rc = c->knobs.gate_hold ? launch_light_gated(c, sc, b, sp) : launch_path_chunks(c, sc, b);
     if (rc != PBRT_OK) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
-    c->ov_done = b.nb;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ov.ev_l2, 0));
+    c->ov.done = b.nb;
     return PBRT_OK;
 }
 // 4: unsplit with overlap: the one chain launch on stream3, the path chunks on stream2 (after overlap_arm).
 int chain_unsplit_overlap(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int kw) {
-    HIPCHK(c, hipStreamWaitEvent(c->stream3, c->ev_split, 0));
-    int rc = launch_ci(c, sc, b, kw, b.nb, b.sched.order, c->stream3, c->d_prog, true);
+    HIPCHK(c, hipStreamWaitEvent(c->ov.stream3, c->ev_split, 0));
+    int rc = launch_ci(c, sc, b, kw, b.nb, b.sched.order, c->ov.stream3, c->ov.d_prog.get(), true);
     if (rc != PBRT_OK) return rc;
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev_l2, c->stream3));
+    HIPCHK(c, hipEventRecord(c->ov.ev_l2, c->ov.stream3));
     if ((rc = launch_path_chunks(c, sc, b)) != PBRT_OK) return rc;
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_l2, 0));
-    c->ov_done = b.nb;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ov.ev_l2, 0));
+    c->ov.done = b.nb;
     return PBRT_OK;
 }
 
@@ -1791,21 +1499,21 @@ int chain_stage(pbrt_gpu_ctx* c, const DevScene& sc, Batch& b) {
         // keyed by the waves per tile; a cached entry brings its heavy count; a frame without a
         // measured order runs the cold-frame probe
         if ((rc = chain_schedule(c, schedule_key(rp, kw), b.nb, true, s)) != PBRT_OK) return rc;
-        c->probed = false;
+        c->sched.probed = false;
         if (!s.order && ci_probe_enabled(c) && b.nb <= (int64_t)1 << 24) {
             if ((rc = probe_order(c, sc, b)) != PBRT_OK) return rc;
-            s.order = c->d_slot_order;
+            s.order = c->sched.d_slot_order.get();
         }
     }
     const Split sp = ci_split(c, b.nb, kw, s.learned, G, kx, mesh_only);
-    c->last_heavy = sp.heavy;
+    c->sched.last_heavy = sp.heavy;
     if (s.ticks) {   // label every slot with the waves it actually runs at
-        c->h_slot_kw.assign((size_t)b.nb, (uint8_t)(sp.heavy > 0 ? sp.light_w : kw));
-        for (int64_t i = 0; i < sp.heavy; i++) c->h_slot_kw[c->h_slot_order[(size_t)i]] = (uint8_t)sp.heavy_w;
+        c->sched.h_slot_kw.assign((size_t)b.nb, (uint8_t)(sp.heavy > 0 ? sp.light_w : kw));
+        for (int64_t i = 0; i < sp.heavy; i++) c->sched.h_slot_kw[c->sched.h_slot_order[(size_t)i]] = (uint8_t)sp.heavy_w;
     }
     // the completion-driven path stage takes EXACT k_paths_ci (path_stage's last case) and a learned order
     const bool paths_ci_exact = !(paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0);
-    const bool ov_ok = c->knobs.paths_overlap > 0 && paths_ci_exact && s.learned && !c->ov_retry && c->ov_stalls < 2;
+    const bool ov_ok = c->knobs.paths_overlap > 0 && paths_ci_exact && s.learned && !c->ov.retry && c->ov.stalls < 2;
     const bool overlap = sp.heavy > 0 && ov_ok;
     // no split: the completion list needs one tile per workgroup
     const bool overlap1 = sp.heavy == 0 && ov_ok && c->knobs.paths_overlap_all && (kw > 1 || G == 1);
@@ -1824,10 +1532,10 @@ int path_stage(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
         const int64_t nrec = b.nb * c->wb.ppt;
         if (rp.spp > 1)
             launch_k(c, c->non_matte ? k_dl_samples<true> : k_dl_samples<false>,
-                     dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave, (int64_t)c->n_simd * 64)),
+                     dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave, (int64_t)c->dev.n_simd * 64)),
                      dim3(kWave), 0, c->stream, with_slot(sc, 3), rp, c->wb, b.sb, nrec);
         launch_k(c, k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, b.sb, nrec,
-                 c->d_ctr);
+                 c->d_ctr.get());
         return PBRT_OK;
     }
     if (paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0) {
@@ -1840,8 +1548,8 @@ int path_stage(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
         launch_mb_setup(c, sc, b);
         return launch_paths(c, sc, b, true, nullptr, b.nb, c->stream);
     }
-    if (c->ov_done > 0) {   // the completion-driven path stage (stream2) ends the chain stage
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_p1, 0));
+    if (c->ov.done > 0) {   // the completion-driven path stage (stream2) ends the chain stage
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->ov.ev_p1, 0));
         return PBRT_OK;
     }
     return launch_paths(c, sc, b, false, nullptr, b.nb, c->stream);
@@ -1858,12 +1566,12 @@ int enqueue_wave(pbrt_gpu_ctx* c, const DevScene& sc) {
     for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
         Batch b{bi, sb, std::min<int64_t>(c->wave_batch, rp.n_slots - sb)};
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
-        c->ov_done = 0;
+        c->ov.done = 0;
         if (c->use_dl) {
             launch_primary(c, sc, b);
             unsigned lds = 0;
             const ChainLayout lw = ci_layout(c->lay_ci, 1, 1, lds);
-            launch_k(c, k_dl_setup, dim3((unsigned)b.nb), dim3(kWave), lds, c->stream, sc, rp, lw, c->d_jump, c->wb,
+            launch_k(c, k_dl_setup, dim3((unsigned)b.nb), dim3(kWave), lds, c->stream, sc, rp, lw, c->d_jump.get(), c->wb,
                      sb, b.nb);
         } else if (!mb) {   // (THROUGHPUT has no offset chain: every sample's stream is known up front)
             if ((rc = chain_stage(c, sc, b)) != PBRT_OK) return rc;
@@ -1888,13 +1596,13 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
     int rc = prepare(c, rd);
     if (rc != PBRT_OK) return rc;
     const RenderParams& rp = c->rp;
-    double* out = film_device ? film_device : c->d_out;
+    double* out = film_device ? film_device : c->d_out.get();
     c->film_target = out;
-    c->last_heavy = 0;
-    c->sched_src = PBRT_SCHED_LAUNCH_ORDER;
-    HIPCHK(c, hipMemsetAsync(c->d_ctr, 0, sizeof(Counters), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_cancel_seen, 0, sizeof(int), c->stream));
-    if (rp.n_slots > 0) HIPCHK(c, hipMemsetAsync(c->d_panics, 0, sizeof(PanicRec) * (size_t)rp.n_slots, c->stream));
+    c->sched.last_heavy = 0;
+    c->sched.src = PBRT_SCHED_LAUNCH_ORDER;
+    HIPCHK(c, hipMemsetAsync(c->d_ctr.get(), 0, sizeof(Counters), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->cancel.d_seen.get(), 0, sizeof(int), c->stream));
+    if (rp.n_slots > 0) HIPCHK(c, hipMemsetAsync(c->d_panics.get(), 0, sizeof(PanicRec) * (size_t)rp.n_slots, c->stream));
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (rp.n_slots > 0) {
         DevScene sc = dev_scene(c, rd->integrator == PBRT_INTEGRATOR_PATH);
@@ -1907,15 +1615,15 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
             const SerialKernel kern = serial_kernel(c->min_waves);
             if (!kern)
                 return set_err(c, PBRT_E_HIP, "no k_render_exact instantiation for occupancy " + std::to_string(c->min_waves));
-            launch_k(c, kern, dim3((unsigned)blocks), dim3(kWave), 0, c->stream, with_slot(sc, 6), rp, c->d_films,
-                     c->d_s1d, c->d_panics, c->d_ctr);
+            launch_k(c, kern, dim3((unsigned)blocks), dim3(kWave), 0, c->stream, with_slot(sc, 6), rp, c->d_films.get(),
+                     c->d_s1d.get(), c->d_panics.get(), c->d_ctr.get());
         }
         HIPCHK(c, hipGetLastError());
     }
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     int64_t npx = rp.film_w * rp.film_h;
-    launch_k(c, k_merge_film, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film, rp,
-             c->d_films, out, c->d_cancel_seen);
+    launch_k(c, k_merge_film, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film.get(), rp,
+             c->d_films.get(), out, c->cancel.d_seen.get());
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipEventRecord(c->ev2, c->stream));
     c->rendered = true;
@@ -1931,17 +1639,10 @@ int pbrt_gpu_synchronize(pbrt_gpu_ctx* c, pbrt_gpu_stats* stats) {
     if (!c) return PBRT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     const hipError_t se = hipStreamSynchronize(c->stream);
-    bool cancelled = false;
-    {   // the render has ended: its cancel flag dies with it
-        std::lock_guard<std::mutex> lk(c->cancel_mu);
-        cancelled = c->in_flight && c->cancel_req;
-        c->in_flight = false;
-        c->cancel_req = false;
-        __atomic_store_n(c->h_cancel, 0, __ATOMIC_SEQ_CST);
-    }
+    const bool cancelled = c->cancel.reset(false);   // the render has ended: its cancel flag dies with it
     HIPCHK(c, se);
     if (cancelled) {   // the kernels stopped early: the film and the schedule feedback are not valid
-        c->ticks_pending = false;
+        c->sched.ticks_pending = false;
         c->rendered = false;
         if (stats) {
             std::memset(stats, 0, sizeof(*stats));
@@ -1952,24 +1653,24 @@ int pbrt_gpu_synchronize(pbrt_gpu_ctx* c, pbrt_gpu_stats* stats) {
         return set_err(c, PBRT_E_CANCELLED, "cancelled by pbrt_gpu_cancel");
     }
     Counters ctr;
-    HIPCHK(c, hipMemcpy(&ctr, c->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&ctr, c->d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost));
     if (ctr.gate_stall) {
         // the completion-driven path stage's gates saw the chains stand still
         // (k_gate): the film misses path work. Render the frame again with the path
         // stage after the chains; the chains replay the same streams, so the
         // result is the one an overlapped frame gives.
-        if (++c->ov_stalls == 2)
+        if (++c->ov.stalls == 2)
             std::fprintf(stderr, "pbrt: k_gate stalled twice (kernels serialised across streams, e.g. by a "
                                  "counter-collecting profiler): the path stage now runs after the chains\n");
-        c->ov_retry = true;
-        const int rr = render_enqueue(c, &c->last_rd, c->last_film_device);
-        c->ov_retry = false;
+        c->ov.retry = true;
+        const int rr = render_enqueue(c, &c->ov.last_rd, c->ov.last_film_device);
+        c->ov.retry = false;
         if (rr != PBRT_OK) return rr;
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipMemcpy(&ctr, c->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(&ctr, c->d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost));
         if (ctr.gate_stall) return set_err(c, PBRT_E_HIP, "k_gate stalled without the overlap");
-    } else if (c->ov_done > 0) {
-        c->ov_stalls = 0;
+    } else if (c->ov.done > 0) {
+        c->ov.stalls = 0;
     }
     float ms = 0, ms_merge = 0;
     (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
@@ -1993,46 +1694,24 @@ int pbrt_gpu_synchronize(pbrt_gpu_ctx* c, pbrt_gpu_stats* stats) {
         st.chain_ms += a;
         st.paths_ms += p;
     }
-    if (c->ticks_pending) {   // heaviest-first slot order for the next frame of this configuration
-        c->ticks_pending = false;
-        std::vector<uint32_t> t((size_t)c->ticks_n);
-        HIPCHK(c, hipMemcpy(t.data(), c->d_ticks, sizeof(uint32_t) * t.size(), hipMemcpyDeviceToHost));
-        c->h_last_ticks = t;   // pbrt_gpu_tile_ticks
+    if (c->sched.ticks_pending) {   // heaviest-first slot order for the next frame of this configuration
+        c->sched.ticks_pending = false;
+        std::vector<uint32_t> t((size_t)c->sched.ticks_n);
+        HIPCHK(c, hipMemcpy(t.data(), c->sched.d_ticks.get(), sizeof(uint32_t) * t.size(), hipMemcpyDeviceToHost));
+        c->sched.h_last_ticks = t;   // pbrt_gpu_tile_ticks
         if (kTickPlanes > 1) {   // diagnostics builds: start and end clocks (pbrt_gpu_tile_clocks)
-            c->h_tick_clocks.resize(2 * t.size());
-            HIPCHK(c, hipMemcpy(c->h_tick_clocks.data(), c->d_ticks + t.size(), sizeof(uint32_t) * 2 * t.size(),
+            c->sched.h_tick_clocks.resize(2 * t.size());
+            HIPCHK(c, hipMemcpy(c->sched.h_tick_clocks.data(), c->sched.d_ticks.get() + t.size(), sizeof(uint32_t) * 2 * t.size(),
                                 hipMemcpyDeviceToHost));
         }
-        // cost at 1 wave per tile: 2 and 4 waves measured 1.3x / 1.8x faster per tile
-        std::vector<double> cost(t.size());
-        double sum = 0;
-        for (size_t i = 0; i < t.size(); i++) {
-            const int w = i < c->h_slot_kw.size() ? c->h_slot_kw[i] : 1;
-            cost[i] = (double)t[i] * (w == 8 ? 2.3 : w == 4 ? 1.8 : w == 2 ? 1.3 : 1.0);
-            sum += cost[i];
-        }
-        c->h_slot_order.resize(t.size());
-        for (size_t i = 0; i < t.size(); i++) c->h_slot_order[i] = (uint32_t)i;
-        std::stable_sort(c->h_slot_order.begin(), c->h_slot_order.end(),
-                         [&](uint32_t a, uint32_t b) { return cost[a] > cost[b]; });
-        // heavy: tiles whose 1-wave chain alone would take over 0.7x the
-        // frame's throughput bound (summed cost over the chain's waves/SIMD)
-        const double thr = 0.7 * sum / ((double)c->ci_wps * (double)c->n_simd);
-        int64_t k = 0;
-        while (k < (int64_t)t.size() && cost[c->h_slot_order[(size_t)k]] > thr) k++;
-        // at most a quarter of the wave slots; at most 1/16 of them when the tiles
-        // outnumber the one-wave slots (one GPU, 1/2 shards), whose light launch then
-        // fills the GPU longer than the heavy tiles take (1/2 of B: 216 -> 202 ms with
-        // 64 against 256; 1/4 of B: best at 256, 126-129 ms against 131-142 at 128-384)
-        const int64_t cap = (int64_t)t.size() > (int64_t)c->ci_wps * c->n_simd ? c->n_simd / 16 : c->n_simd / 4;
-        c->heavy_k = std::min<int64_t>(k, cap);
-        if (ci_heavy_override(c) >= 0) c->heavy_k = ci_heavy_override(c);
-        c->order_key = c->ticks_key;
-        if (ci_order_cache(c)) sched_cache_put(c, c->ticks_key, c->h_slot_order, c->heavy_k);
+        c->sched.heavy_k = learn_order(t, c->sched.h_slot_kw, c->sched.ci_wps, c->dev.n_simd, ci_heavy_override(c),
+                                       c->sched.h_slot_order);   // schedule.h
+        c->sched.order_key = c->sched.ticks_key;
+        if (ci_order_cache(c)) sched_cache_put(sched_cache_key(c, c->sched.ticks_key), c->sched.h_slot_order, c->sched.heavy_k);
     }
     if (ctr.any_panic) {
         std::vector<PanicRec> pr((size_t)c->rp.n_slots);
-        HIPCHK(c, hipMemcpy(pr.data(), c->d_panics, sizeof(PanicRec) * pr.size(), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(pr.data(), c->d_panics.get(), sizeof(PanicRec) * pr.size(), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < pr.size(); i++) {
             if (pr[i].kind == 0) continue;
             st.panic_kind = pr[i].kind;
@@ -2065,13 +1744,13 @@ int pbrt_gpu_render(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_xy
     return PBRT_OK;
 }
 
-double* pbrt_gpu_film_device(pbrt_gpu_ctx* c) { return c ? c->d_out : nullptr; }
+double* pbrt_gpu_film_device(pbrt_gpu_ctx* c) { return c ? c->d_out.get() : nullptr; }
 void* pbrt_gpu_stream(pbrt_gpu_ctx* c) { return c ? (void*)c->stream : nullptr; }
 
 int pbrt_gpu_film_download(pbrt_gpu_ctx* c, double* film_xyz) {
     if (!c || !film_xyz || !c->rendered) return PBRT_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpy(film_xyz, c->film_target ? c->film_target : c->d_out,
+    HIPCHK(c, hipMemcpy(film_xyz, c->film_target ? c->film_target : c->d_out.get(),
                         sizeof(double) * (size_t)(c->rp.film_w * c->rp.film_h * 3),
                         hipMemcpyDeviceToHost));
     return PBRT_OK;
@@ -2090,12 +1769,10 @@ static int intersect_batch(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, 
         q[6] = rays->tmax ? rays->tmax[i] : gomath::kInf;
     }
     size_t nout = any ? n : 9 * n;
-    double *d_in = nullptr, *d_o = nullptr;
-    HIPCHK(c, hipMalloc((void**)&d_in, sizeof(double) * packed.size()));
-    if (hipMalloc((void**)&d_o, sizeof(double) * nout) != hipSuccess) {
-        (void)hipFree(d_in);
-        return set_err(c, PBRT_E_HIP, "hipMalloc");
-    }
+    DevBuf<double> in_buf, out_buf;
+    if (int rc = in_buf.ensure(c, packed.size())) return rc;
+    if (int rc = out_buf.ensure(c, nout)) return rc;
+    double *d_in = in_buf.get(), *d_o = out_buf.get();
     std::vector<double> o(nout);
     hipError_t e = hipMemcpyAsync(d_in, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
@@ -2107,8 +1784,6 @@ static int intersect_batch(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, 
     }
     if (e == hipSuccess) e = hipMemcpyAsync(o.data(), d_o, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_o);
     if (e != hipSuccess) return set_err(c, PBRT_E_HIP, hipGetErrorString(e));
     int rc = PBRT_OK;
     for (size_t i = 0; i < n; i++) {
@@ -2145,19 +1820,19 @@ int pbrt_gpu_intersect_p(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, ui
 // context's counters and buffers, and its kernels may be waiting on one another
 // across the context's streams.
 static bool query_blocked(pbrt_gpu_ctx* c) {
-    std::lock_guard<std::mutex> lk(c->cancel_mu);
-    return c->in_flight;
+    std::lock_guard<std::mutex> lk(c->cancel.mu);
+    return c->cancel.in_flight;
 }
 // the record cleared, in stream order (so after the queries already enqueued)
 static hipError_t query_rec_clear(pbrt_gpu_ctx* c) {
-    hipError_t e = hipMemsetAsync(&c->d_qrec->panics, 0, sizeof(c->d_qrec->panics), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(&c->d_qrec->first, 0xFF, sizeof(c->d_qrec->first), c->stream);
+    hipError_t e = hipMemsetAsync(&c->d_qrec.get()->panics, 0, sizeof(c->d_qrec.get()->panics), c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(&c->d_qrec.get()->first, 0xFF, sizeof(c->d_qrec.get()->first), c->stream);
     return e;
 }
 // the one allocation of the query path, on a context's first query
 static int query_rec_ensure(pbrt_gpu_ctx* c) {
-    if (c->d_qrec) return PBRT_OK;
-    HIPCHK(c, hipMalloc((void**)&c->d_qrec, sizeof(QueryRec)));
+    if (c->d_qrec.get()) return PBRT_OK;
+    if (int rc = c->d_qrec.ensure(c, 1)) return rc;
     HIPCHK(c, query_rec_clear(c));
     return PBRT_OK;
 }
@@ -2179,10 +1854,10 @@ static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool a
     const dim3 grid((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
     const bool mesh_only = c->host_scene.n_prims == 0;   // as the render path chooses its kMeshOnly kernels
 #define PBRT_QUERY_LAUNCH(A, M) \
-    launch_k(c, (k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec)
+    launch_k(c, (k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get())
     if (staged) {
-        if (any) launch_k(c, k_query_hit_staged<true>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec);
-        else launch_k(c, k_query_hit_staged<false>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec);
+        if (any) launch_k(c, k_query_hit_staged<true>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get());
+        else launch_k(c, k_query_hit_staged<false>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get());
     } else if (any) {
         if (mesh_only) PBRT_QUERY_LAUNCH(true, true);
         else PBRT_QUERY_LAUNCH(true, false);
@@ -2229,7 +1904,7 @@ int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d,
     if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
     HIPCHK(c, hipSetDevice(c->device));
     launch_k(c, k_query_camera, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0,
-                       c->stream, c->d_camera, *d, *rays);
+                       c->stream, c->d_camera.get(), *d, *rays);
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
 }
@@ -2240,8 +1915,8 @@ int pbrt_gpu_query_status(pbrt_gpu_ctx* c, pbrt_query_record* out) {
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     QueryRec rec{0, ~0ull};
-    if (c->d_qrec) {
-        HIPCHK(c, hipMemcpy(&rec, c->d_qrec, sizeof(rec), hipMemcpyDeviceToHost));
+    if (c->d_qrec.get()) {
+        HIPCHK(c, hipMemcpy(&rec, c->d_qrec.get(), sizeof(rec), hipMemcpyDeviceToHost));
         if (rec.panics) HIPCHK(c, query_rec_clear(c));
     }
     if (out) {
@@ -2302,27 +1977,20 @@ void pbrt_gpu_buffer_destroy(pbrt_gpu_buffer* b) {
 
 void pbrt_gpu_cancel(pbrt_gpu_ctx* c) {
     if (!c) return;
-    std::lock_guard<std::mutex> lk(c->cancel_mu);
-    if (!c->in_flight) return;   // nothing to cancel: no render is in flight
-    c->cancel_req = true;
-    __atomic_store_n(c->h_cancel, 1, __ATOMIC_SEQ_CST);
+    std::lock_guard<std::mutex> lk(c->cancel.mu);
+    if (!c->cancel.in_flight) return;   // nothing to cancel: no render is in flight
+    c->cancel.req = true;
+    __atomic_store_n(c->cancel.h_flag, 1, __ATOMIC_SEQ_CST);
 }
 const char* pbrt_gpu_last_error(const pbrt_gpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 void pbrt_gpu_destroy(pbrt_gpu_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (hipStream_t st : {c->stream, c->stream2, c->stream3})
+    for (hipStream_t st : {c->stream, c->stream2, c->ov.stream3})
         if (st) (void)hipStreamSynchronize(st);
-    void* bufs[] = {c->d_shapes, c->d_materials, c->d_prims, c->d_nodes, c->d_order, c->d_lights, c->d_camera, c->d_film,
-                    c->d_dist,   c->d_films,     c->d_s1d,   c->d_panics, c->d_ctr,   c->d_out,    c->d_jump,
-                    c->d_wave,   c->d_fprims, c->d_ticks, c->d_slot_order, c->d_groups,
-                    c->d_gmasks, c->d_cost,   c->d_cost_keys, c->d_pw, c->d_cancel_seen, c->d_prog};
-    for (void* b : bufs)
-        if (b) (void)hipFree(b);
     // the caller's buffers that are still alive (the streams are idle by now)
     pbrtq::list_free_all(c->qbufs, [](void* p) { (void)hipFree(p); });
-    if (c->d_qrec) (void)hipFree(c->d_qrec);
     mesh_bvh_free(c->mesh);
     for (hipEvent_t e : c->bev) (void)hipEventDestroy(e);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -2330,26 +1998,26 @@ void pbrt_gpu_destroy(pbrt_gpu_ctx* c) {
     if (c->ev2) (void)hipEventDestroy(c->ev2);
     if (c->ev_split) (void)hipEventDestroy(c->ev_split);
     if (c->ev_join) (void)hipEventDestroy(c->ev_join);
-    for (hipEvent_t e : {c->ev_l2, c->ev_p1})
+    for (hipEvent_t e : {c->ov.ev_l2, c->ov.ev_p1})
         if (e) (void)hipEventDestroy(e);
-    if (c->stream3) {
-        (void)hipStreamSynchronize(c->stream3);
-        (void)hipStreamDestroy(c->stream3);
+    if (c->ov.stream3) {
+        (void)hipStreamSynchronize(c->ov.stream3);
+        (void)hipStreamDestroy(c->ov.stream3);
     }
     if (c->stream2) {
         (void)hipStreamSynchronize(c->stream2);
         (void)hipStreamDestroy(c->stream2);
     }
     if (c->stream) (void)hipStreamDestroy(c->stream);
-    if (c->h_cancel) (void)hipHostFree(c->h_cancel);
-    delete c;
+    if (c->cancel.h_flag) (void)hipHostFree(c->cancel.h_flag);
+    delete c;   // every DevBuf frees its allocation
 }
 
 }  // extern "C"
 
 // what a device group (group.hip) reads of a member after its frame
 pbrtk::GroupMemberView pbrt_group_member_view(const pbrt_gpu_ctx* c) {
-    return pbrtk::GroupMemberView{c->device, c->d_films, c->d_film, &c->host_scene.film, c->rp};
+    return pbrtk::GroupMemberView{c->device, c->d_films.get(), c->d_film.get(), &c->host_scene.film, c->rp};
 }
 
 extern "C" {
@@ -2445,12 +2113,10 @@ extern "C" int pbrt_gpu_probe(int device, int op, const double* in, size_t n, in
     if (!in || !out || in_stride <= 0 || out_stride <= 0) return PBRT_E_INVALID;
     if (n == 0) return PBRT_OK;
     if (device >= 0 && hipSetDevice(device) != hipSuccess) return PBRT_E_HIP;
-    double *d_in = nullptr, *d_out = nullptr;
-    if (hipMalloc((void**)&d_in, sizeof(double) * n * in_stride) != hipSuccess) return PBRT_E_HIP;
-    if (hipMalloc((void**)&d_out, sizeof(double) * n * out_stride) != hipSuccess) {
-        (void)hipFree(d_in);
+    DevBuf<double> in_buf, out_buf;
+    if (in_buf.ensure(nullptr, n * in_stride) != PBRT_OK || out_buf.ensure(nullptr, n * out_stride) != PBRT_OK)
         return PBRT_E_HIP;
-    }
+    double *d_in = in_buf.get(), *d_out = out_buf.get();
     hipError_t e = hipMemcpy(d_in, in, sizeof(double) * n * in_stride, hipMemcpyHostToDevice);
     if (e == hipSuccess) {
         launch_logged(nullptr, 0, k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (int64_t)n,
@@ -2458,8 +2124,6 @@ extern "C" int pbrt_gpu_probe(int device, int op, const double* in, size_t n, in
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * n * out_stride, hipMemcpyDeviceToHost);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
     return e == hipSuccess ? PBRT_OK : PBRT_E_HIP;
 }
 
@@ -2467,7 +2131,7 @@ extern "C" int pbrt_gpu_counters(pbrt_gpu_ctx* c, uint64_t* out, int n) {
     if (!c || !out) return PBRT_E_INVALID;
     if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return PBRT_E_HIP;
     Counters ctr;
-    if (hipMemcpy(&ctr, c->d_ctr, sizeof(ctr), hipMemcpyDeviceToHost) != hipSuccess) return PBRT_E_HIP;
+    if (hipMemcpy(&ctr, c->d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost) != hipSuccess) return PBRT_E_HIP;
     const uint64_t v[kNumCounters] = {ctr.paths,    ctr.camera_samples, ctr.closest_rays, ctr.shadow_rays,
                                       (uint64_t)ctr.any_panic, ctr.windows, ctr.phase[0], ctr.phase[1],
                                       ctr.phase[2], ctr.phase[3], ctr.phase[4], ctr.phase[5],
@@ -2517,30 +2181,29 @@ extern "C" int pbrt_gpu_mesh_download(pbrt_gpu_ctx* c, void* nodes, int32_t* gid
 
 extern "C" int64_t pbrt_gpu_tile_clocks(pbrt_gpu_ctx* c, uint32_t* start, uint32_t* end, int64_t n) {
     if (!c) return -PBRT_E_INVALID;
-    const int64_t m = (int64_t)c->h_tick_clocks.size() / 2;
+    const int64_t m = (int64_t)c->sched.h_tick_clocks.size() / 2;
     for (int64_t i = 0; i < m && i < n; i++) {
-        if (start) start[i] = c->h_tick_clocks[(size_t)i];
-        if (end) end[i] = c->h_tick_clocks[(size_t)(m + i)];
+        if (start) start[i] = c->sched.h_tick_clocks[(size_t)i];
+        if (end) end[i] = c->sched.h_tick_clocks[(size_t)(m + i)];
     }
     return m;
 }
 
 extern "C" int64_t pbrt_gpu_tile_ticks(pbrt_gpu_ctx* c, uint32_t* out, int64_t n, int64_t* heavy) {
     if (!c) return -PBRT_E_INVALID;
-    if (heavy) *heavy = c->last_heavy;
-    const int64_t m = (int64_t)c->h_last_ticks.size();
-    for (int64_t i = 0; out && i < n && i < m; i++) out[i] = c->h_last_ticks[(size_t)i];
+    if (heavy) *heavy = c->sched.last_heavy;
+    const int64_t m = (int64_t)c->sched.h_last_ticks.size();
+    for (int64_t i = 0; out && i < n && i < m; i++) out[i] = c->sched.h_last_ticks[(size_t)i];
     return m;
 }
 
 extern "C" void pbrt_gpu_schedule_cache_clear(void) {
-    std::lock_guard<std::mutex> lk(g_sched_mu);
-    g_sched.clear();
+    sched_cache_clear();
 }
 
 extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
     if (!c) return -PBRT_E_INVALID;
-    return c->ov_done;
+    return c->ov.done;
 }
 
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
@@ -2671,23 +2334,23 @@ extern "C" int64_t pbrt_gpu_launch_log(pbrt_gpu_ctx* c, int which, pbrt_launch_r
     return m;
 }
 
-extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->lds_per_block : -PBRT_E_INVALID; }
+extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->dev.lds_per_block : -PBRT_E_INVALID; }
 
 extern "C" int pbrt_gpu_schedule_source(pbrt_gpu_ctx* c) {
     if (!c) return -PBRT_E_INVALID;
-    return c->sched_src;
+    return c->sched.src;
 }
 
 extern "C" int64_t pbrt_gpu_tile_costs(pbrt_gpu_ctx* c, float* out, int64_t n) {
     if (!c) return -PBRT_E_INVALID;
-    if (!c->probed || !c->d_cost) return 0;
+    if (!c->sched.probed || !c->sched.d_cost.get()) return 0;
     if (out && n > 0) {
-        const int64_t m = std::min<int64_t>(n, c->cost_n);
+        const int64_t m = std::min<int64_t>(n, c->sched.cost_n);
         if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(out, c->d_cost, sizeof(float) * 4 * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess)
+            hipMemcpy(out, c->sched.d_cost.get(), sizeof(float) * 4 * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess)
             return -PBRT_E_HIP;
     }
-    return c->cost_n;
+    return c->sched.cost_n;
 }
 
 // Region cycles of trajectory steps (PBRT_STEP_TIMING builds only; else zeros):

@@ -84,7 +84,7 @@ def test_the_scene_is_what_the_routes_need():
 
 
 def test_a_disk_is_refused_as_an_area_lights_shape():
-    """pbrt_gpu_create takes spheres as area lights (render.hip validate_scene): PBRT_E_UNSUPPORTED."""
+    """pbrt_gpu_create takes spheres as area lights (scene_tables.h validate_scene): PBRT_E_UNSUPPORTED."""
     with pytest.raises(G.PbrtError) as e:
         G.Renderer(R.disk_light_scene())
     assert e.value.code == abi.PBRT_E_UNSUPPORTED

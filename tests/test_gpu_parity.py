@@ -751,7 +751,7 @@ def test_cornell_256spp_throughput_mode():
 
 @pytest.mark.parametrize("cull", ["0", "1"])
 def test_leaf_culling_groups_keep_bits(cull, monkeypatch):
-    """The README tree's leaf culling groups (cull_groups in render.hip) only
+    """The README tree's leaf culling groups (cull_groups in scene_tables.h) only
     skip leaf tests that fail; with and without them the films are the
     oracle's (EXACT and THROUGHPUT)."""
     monkeypatch.setenv("PBRT_CULL_GROUPS", cull)

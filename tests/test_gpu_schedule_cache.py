@@ -1,4 +1,4 @@
-"""The process-wide schedule cache (render.hip, sched_cache_*).
+"""The process-wide schedule cache (schedule.h, sched_cache_*).
 
 internal/render/server.go:29-164 builds a fresh scene, integrator and renderer
 for every request. A fresh context therefore starts from the schedule another

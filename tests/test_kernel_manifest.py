@@ -94,7 +94,7 @@ def test_cases_are_small_and_their_knobs_exist():
     """At most 64x48 pixels and 3x3 spp (on the one-tile 16x16 image: the windowed StartPixel's
     11x11 without jitter, and the 6x6 that k_paths_cam<4> needs, which runs from 33 spp);
     every knob a case sets is one Knobs::from_env reads, every option one the Renderer takes."""
-    host = open(os.path.join(M.AMD, "csrc", "render.hip")).read()
+    host = open(os.path.join(M.AMD, "csrc", "knobs.h")).read()
     knobs = set(re.findall(r'getenv\("(PBRT_\w+)"\)', host)) | set(re.findall(r'ival\("(PBRT_\w+)"', host))
     assert len(knobs) >= 27
     for name, c in K.CASES.items():
