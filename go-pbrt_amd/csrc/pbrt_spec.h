@@ -214,7 +214,13 @@ __device__ __forceinline__ void add_rays(PathStateLds& s, uint32_t v) { *s.rays 
 // kX: scenes with Mirror, smooth Glass or OrenNayar materials (BSDFX,
 // bsdfx_sample_f, Path.Li's etaScale; rough glass stays on the serial kernel).
 // kX = false is the Matte-only code, unchanged.
-template <int kWhich = 0, bool kX = false, class Cache, class State>
+//
+// kZeroPdf (k_li only): the light distribution may give the picked light pdf 0
+// (the reference's Power strategy: every entry is 0, SURVEY #28).
+// UniformSampleOneLight then returns black after its one draw
+// (integrator.go:56-58): no uLight, no uScattering, no estimate. false: the
+// launch precondition "every light's pdf > 0" holds and no code is generated.
+template <int kWhich = 0, bool kX = false, bool kZeroPdf = false, class Cache, class State>
 __device__ __forceinline__ bool path_step(const DevScene& sc, const Cache& pc, const SpecSampler& ss, Cursor& c,
                                  State& s, int max_depth, double rr_threshold, uint16_t* stack, int& panic,
                                  int& bounce) {
@@ -256,32 +262,38 @@ __device__ __forceinline__ bool path_step(const DevScene& sc, const Cache& pc, c
             add_L(s, smul(s.beta, spec(0)));
         } else {
             int ln;
+            bool picked = true;
             if (sc.dist) {
-                double lpdf;   // > 0 for every light (launch precondition)
+                double lpdf;   // > 0 for every light (launch precondition), but with kZeroPdf
                 ln = sample_discrete(*sc.dist, c_get1d(c, ss), lpdf);
+                if constexpr (kZeroPdf) picked = lpdf != 0.0;
             } else {
                 ln = (int)gomath::to_int(gomath::min(c_get1d(c, ss) * (double)nl, (double)(nl - 1)));
             }
-            // bounce 1's light sample is the pixel's cached estimate where uLight is
-            // the stratified (0,0) (n_dims >= 3); with fewer sampled dims it is a
-            // PCG32 draw per sample, estimated here like any later bounce's
-            const bool ul_strat = c.cur2d < ss.ndims;
-            V2 ul = c_get2d(c, ss);
-            c_get2d(c, ss);
-            if (first && ul_strat) {
-                const Spec ld = pc.ld[ln];
-                const int lp = pc.ld_panic[ln];
-                if (lp & kLdTraced) add_rays(s, kRayShadow);
-                if (lp & 0xFFFF) {
-                    panic = lp & 0xFFFF;
-                    return true;
-                }
-                add_L(s, smul(s.beta, ld));
+            if (kZeroPdf && !picked) {
+                add_L(s, smul(s.beta, spec(0)));
             } else {
-                pending = true;
-                shadow = kX ? estimate_direct_begin_x(sc, isect, b, x, ln, ul, sr, ld_vis)
-                            : estimate_direct_begin(sc, isect, b, ln, ul, sr, ld_vis);
-                if constexpr (kLdsAux) s.aux[1] = ld_vis;
+                // bounce 1's light sample is the pixel's cached estimate where uLight is
+                // the stratified (0,0) (n_dims >= 3); with fewer sampled dims it is a
+                // PCG32 draw per sample, estimated here like any later bounce's
+                const bool ul_strat = c.cur2d < ss.ndims;
+                V2 ul = c_get2d(c, ss);
+                c_get2d(c, ss);
+                if (first && ul_strat) {
+                    const Spec ld = pc.ld[ln];
+                    const int lp = pc.ld_panic[ln];
+                    if (lp & kLdTraced) add_rays(s, kRayShadow);
+                    if (lp & 0xFFFF) {
+                        panic = lp & 0xFFFF;
+                        return true;
+                    }
+                    add_L(s, smul(s.beta, ld));
+                } else {
+                    pending = true;
+                    shadow = kX ? estimate_direct_begin_x(sc, isect, b, x, ln, ul, sr, ld_vis)
+                                : estimate_direct_begin(sc, isect, b, ln, ul, sr, ld_vis);
+                    if constexpr (kLdsAux) s.aux[1] = ld_vis;
+                }
             }
         }
     }

@@ -47,6 +47,7 @@
 #include "../../include/pbrt_scene.h"
 #include "knobs.h"
 #include "mesh_bvh.h"
+#include "li_query.h"
 #include "query_buffers.h"
 #include "render_kernels.h"
 #include "scene_tables.h"
@@ -253,6 +254,13 @@ struct pbrt_gpu_ctx {
     // the queries since the last pbrt_gpu_query_status (allocated by the first)
     pbrtq::BufferList qbufs;
     DevBuf<QueryRec> d_qrec;
+    // pbrt_gpu_li_device: the light distribution of the strategy last queried, in a buffer of the
+    // query's own (a frame uploads its strategy's to d_dist), uploaded when the strategy changes
+    struct {
+        DevBuf<pbrt_distribution_desc> d_dist;
+        pbrt_distribution_desc host_dist;
+        int strategy = 0;   // the strategy d_dist holds (0: none yet)
+    } li;
     // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
     // (cleared by render_enqueue) and those outside a frame (LBVH build, queries)
     LaunchLog log_frame, log_aux;
@@ -609,6 +617,17 @@ const PathsCamRow kPathsCamKernels[] = {   // stack: the k_paths_cam_stack kerne
 PathsCamKernel paths_cam_kernel(int P, bool mb, bool stack) {
     for (const PathsCamRow& r : kPathsCamKernels)
         if (r.P == P && r.mb == mb && r.stack == stack) return r.fn;
+    return nullptr;
+}
+
+using LiKernel = decltype(&k_li<false, 0>);
+struct LiRow { bool kx; int depth; LiKernel fn; const char* name; };
+#define LI_ROW(kx, depth) {kx, depth, &k_li<kx, depth>, "k_li<" #kx ", " #depth ">"}
+const LiRow kLiKernels[] = {LI_ROW(false, 0), LI_ROW(true, 0), LI_ROW(false, 64), LI_ROW(true, 64)};
+#undef LI_ROW
+LiKernel li_kernel(bool kx, int depth) {   // pbrt_gpu_li_device: kDepth 0 on an LDS-staged tree, 64 beyond
+    for (const LiRow& r : kLiKernels)
+        if (r.kx == kx && r.depth == depth) return r.fn;
     return nullptr;
 }
 
@@ -1909,6 +1928,43 @@ int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d,
     return PBRT_OK;
 }
 
+// Integrator.Li over device arrays (k_li.hip). The checks and the kernel choice: li_query.h.
+int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng,
+                       size_t n, const pbrt_radiance_soa* out) {
+    const char* why = "";
+    if (int rc = pbrtli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
+    const bool new_dist = c->li.strategy != d->light_strategy;
+    if (new_dist) {   // (a refused strategy leaves the uploaded one in place)
+        pbrt_distribution_desc dist;
+        if (int rc = pbrt_scene_light_distribution(&c->host_scene, d->light_strategy, &dist))
+            return set_err(c, rc, "unsupported light sample strategy");
+        if (int rc = pbrtli::check_distribution(c->host_scene.n_lights, dist.func, dist.count, dist.func_int, &why))
+            return set_err(c, rc, why);
+        if (n == 0) return PBRT_OK;
+        HIPCHK(c, hipSetDevice(c->device));
+        if (int rc = c->li.d_dist.ensure(c, 1)) return rc;
+        c->li.host_dist = dist;
+        c->li.strategy = 0;
+        HIPCHK(c, hipMemcpyAsync(c->li.d_dist.get(), &c->li.host_dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
+        c->li.strategy = d->light_strategy;
+    }
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = query_rec_ensure(c)) return rc;
+    DevScene sc = with_slot(dev_scene(c, false), 7);
+    sc.dist = c->li.d_dist.get();
+    const pbrtli::KernelArgs ka =
+        pbrtli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
+    const LiKernel kern = li_kernel(ka.kx, ka.depth);
+    if (!kern) return set_err(c, PBRT_E_HIP, "no k_li instantiation for depth " + std::to_string(ka.depth));
+    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
+             *rays, *rng, *out, c->d_qrec.get());
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
 int pbrt_gpu_query_status(pbrt_gpu_ctx* c, pbrt_query_record* out) {
     if (!c) return PBRT_E_INVALID;
     if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
@@ -2209,7 +2265,7 @@ extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
 // kernel the library compiles, spelled as its explicit instantiation is
 // (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
-// k_paths_ci and k_paths_cam[_stack] families are named by their selectors' tables.
+// k_paths_ci, k_paths_cam[_stack] and k_li families are named by their selectors' tables.
 namespace {
 const KernelName kKernelNames[] = {
     // k_paths_m.hip, k_paths_x.hip
@@ -2274,6 +2330,7 @@ void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' ta
     for (const ChainRow& r : kChainKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const PathsCiRow& r : kPathsCiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const LiRow& r : kLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const KernelName& k : kKernelNames) f(k.fn, k.name);
     size_t nm = 0;
     const KernelName* mk = mesh_bvh_kernel_names(&nm);
@@ -2307,6 +2364,8 @@ extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a,
         fn = reinterpret_cast<const void*>(paths_cam_kernel(a[0], a[1] != 0, a[2] != 0));
     else if (f == "k_render_exact" && n == 1)
         fn = reinterpret_cast<const void*>(serial_kernel(a[0]));
+    else if (f == "k_li" && n == 2)
+        fn = reinterpret_cast<const void*>(li_kernel(a[0] != 0, a[1]));
     return fn ? kernel_name_of(fn, nullptr) : nullptr;
 }
 

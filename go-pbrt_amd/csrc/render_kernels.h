@@ -60,5 +60,8 @@ __global__ void k_query_hit(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_
 template <bool kAny>
 __global__ void k_query_hit_staged(DevScene sc, int64_t n, pbrt_ray_soa rays, pbrt_hit_soa hits, QueryRec* __restrict__ rec);
 __global__ void k_query_camera(const pbrt_camera_desc* __restrict__ cam, pbrt_camera_rays_desc d, pbrt_ray_soa_out out);
+// batched Integrator.Li over device arrays (pbrt_gpu_li_device): k_li.hip
+template <bool kX, int kDepth>
+__global__ void k_li(DevScene sc, int max_depth, double rr_threshold, int64_t n, pbrt_ray_soa rays, pbrt_rng_soa rng, pbrt_radiance_soa out, QueryRec* __restrict__ rec);
 
 }  // namespace pbrtk

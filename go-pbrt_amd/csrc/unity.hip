@@ -18,5 +18,6 @@
 #include "k_frame.hip"
 #include "k_group.hip"
 #include "k_query.hip"
+#include "k_li.hip"
 #include "render.hip"
 #include "group.hip"

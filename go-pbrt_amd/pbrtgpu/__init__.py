@@ -66,6 +66,8 @@ def lib():
     L.pbrt_gpu_destroy.restype = None
     abi.declare_group(L)
     abi.declare_query(L)
+    if hasattr(L, "pbrt_gpu_li_device"):   # (a library of an earlier build, PBRT_GPU_LIB, has no such entry)
+        abi.declare_li(L)
     abi.declare_launch_log(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
     L.pbrt_gpu_tile_ticks.argtypes = [C.c_void_p, P(C.c_uint32), i64, P(i64)]
@@ -445,14 +447,18 @@ class ContextToken:
         self.alive = True
 
 
-BUFFER_DTYPES = (np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.uint8))
+BUFFER_DTYPES = (np.dtype(np.float64), np.dtype(np.int32), np.dtype(np.uint8), np.dtype(np.uint64),
+                 np.dtype(np.uint32))
 RAY_KEYS = ("ox", "oy", "oz", "dx", "dy", "dz")
 HIT_DTYPES = {"hit": np.uint8, "t_max": np.float64, "prim": np.int32, "px": np.float64, "py": np.float64,
               "pz": np.float64, "nx": np.float64, "ny": np.float64, "nz": np.float64}
+RNG_KEYS = ("state", "inc")
+LI_DTYPES = {"r": np.float64, "g": np.float64, "b": np.float64, "state": np.uint64, "draws": np.uint32,
+             "rays": np.uint32}
 
 
 class DeviceBuffer:
-    """pbrt_gpu_buffer: n elements of float64, int32 or uint8 in device memory
+    """pbrt_gpu_buffer: n elements of float64, int32, uint8, uint64 or uint32 in device memory
     that the Renderer's context owns. Made by Renderer.buffer / Renderer.upload.
     It keeps its Renderer alive; once that Renderer is closed the buffer is
     closed too (its memory went with the context): close() and deletion then do
@@ -725,10 +731,11 @@ class Renderer:
     # ---- device-resident queries: numpy and ctypes only; the device memory is
     # the context's own (DeviceBuffer), so nothing here can outlive the context
     def buffer(self, n, dtype=np.float64):
-        """A DeviceBuffer of n elements (float64, int32 or uint8), uninitialised."""
+        """A DeviceBuffer of n elements (float64, int32, uint8, uint64 or uint32), uninitialised."""
         dtype = np.dtype(dtype)
         if dtype not in BUFFER_DTYPES or n <= 0:
-            raise PbrtError(abi.PBRT_E_INVALID, f"buffer of {n} x {dtype}: float64, int32 or uint8, n > 0")
+            raise PbrtError(abi.PBRT_E_INVALID,
+                            f"buffer of {n} x {dtype}: float64, int32, uint8, uint64 or uint32, n > 0")
         if not getattr(self, "h", None):
             raise PbrtError(abi.PBRT_E_INVALID, "the Renderer is closed")
         h = C.c_void_p()
@@ -788,6 +795,60 @@ class Renderer:
         rs = _soa(abi.RaySoAOut, rb)
         self._check(lib().pbrt_gpu_camera_rays_device(self.h, C.byref(d), C.byref(rs)))
         return {k: b for k, b, _ in rb}
+
+    def li_device(self, rays, rng, n, out, max_depth=10, light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM,
+                  rr_threshold=1.0, integrator=abi.PBRT_INTEGRATOR_PATH):
+        """pbrt_gpu_li_device: Path.Li of rays[0:n], ray i on the PCG32 stream (rng["state"][i],
+        rng["inc"][i]) (uint64 buffers; a dict or a pair), into the buffers of out: r, g, b
+        (float64, required) and any of state (uint64: the stream after the path), draws (uint32:
+        its PCG32 draws) and rays (uint32: closest | shadow << 16). Enqueue only, like
+        intersect_device; a ray on which the reference panics has L = 0 and is counted in
+        query_status(). Returns the status (PBRT_E_UNSUPPORTED: last_error() says why)."""
+        if not isinstance(rng, dict):
+            rng = dict(zip(RNG_KEYS, tuple(rng)))
+        unknown = (set(out) - set(LI_DTYPES)) | (set(rng) - set(RNG_KEYS))
+        missing = [k for k in ("r", "g", "b") if out.get(k) is None] + [k for k in RNG_KEYS if rng.get(k) is None]
+        if unknown or missing:
+            raise PbrtError(abi.PBRT_E_INVALID, f"li_device: unknown {sorted(unknown)}, missing {missing}")
+        rb = _ray_bufs(rays)
+        gb = [(k, rng[k], np.uint64) for k in RNG_KEYS]
+        ob = [(k, out[k], dt) for k, dt in LI_DTYPES.items() if out.get(k) is not None]
+        check_buffers(self, n, rb + gb + ob)
+        d = abi.li_desc(max_depth, light_strategy, rr_threshold, integrator)
+        rs, gs, os_ = _soa(abi.RaySoA, rb), _soa(abi.RngSoA, gb), _soa(abi.RadianceSoA, ob)
+        return lib().pbrt_gpu_li_device(self.h, C.byref(d), C.byref(rs), C.byref(gs), n, C.byref(os_))
+
+    def last_error(self):
+        """pbrt_gpu_last_error: the reason of the context's last refusal."""
+        return lib().pbrt_gpu_last_error(self.h).decode()
+
+    def radiance(self, rays, state, inc, **desc):
+        """Path.Li of host rays: rays is (n, 6) [ox, oy, oz, dx, dy, dz] or (n, 7) with tmax,
+        state and inc the PCG32 stream of each ray (uint64). Uploads, queries and downloads;
+        desc is li_device's (max_depth, light_strategy, rr_threshold). Returns (L (n, 3),
+        state, draws, rays); raises PbrtError on a refusal and PBRT_E_REF_PANIC when the
+        reference panics on a ray (its stats field is the QueryRecord)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        n = rays.shape[0]
+        if rays.ndim != 2 or rays.shape[1] not in (6, 7) or len(state) != n or len(inc) != n:
+            raise PbrtError(abi.PBRT_E_INVALID, "radiance: rays (n, 6) or (n, 7), state and inc of n elements")
+        if n == 0:
+            return np.zeros((0, 3)), np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
+        bufs = []
+        try:
+            rb = [self.upload(rays[:, k]) for k in range(rays.shape[1])]
+            gb = [self.upload(np.asarray(a, dtype=np.uint64)) for a in (state, inc)]
+            ob = {k: self.buffer(n, dt) for k, dt in LI_DTYPES.items()}
+            bufs = rb + gb + list(ob.values())
+            self._check(self.li_device(tuple(rb), tuple(gb), n, ob, **desc))
+            rc, rec = self.query_status()
+            if rc:
+                raise PbrtError(rc, self.last_error(), rec)
+            got = {k: b.download() for k, b in ob.items()}
+        finally:
+            for b in bufs:
+                b.close()
+        return np.stack([got["r"], got["g"], got["b"]], axis=1), got["state"], got["draws"], got["rays"]
 
     def query_status(self):
         """(status, QueryRecord) of the queries since the last call: synchronises

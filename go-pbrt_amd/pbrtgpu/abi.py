@@ -389,3 +389,37 @@ def declare_query(L):
     L.pbrt_gpu_cull_groups.argtypes = [vp]
     L.pbrt_gpu_camera_rays_device.argtypes = [vp, P(CameraRaysDesc), P(RaySoAOut)]
     L.pbrt_gpu_query_status.argtypes = [vp, P(QueryRecord)]
+
+
+# ------------------------------------------------- batched Integrator.Li queries
+class LiDesc(C.Structure):
+    """pbrt_li_desc: what pbrt_gpu_li_device needs of a render desc."""
+    _fields_ = [("integrator", C.c_int32), ("max_depth", C.c_int32), ("light_strategy", C.c_int32),
+                ("reserved", C.c_int32), ("rr_threshold", C.c_double)]
+
+
+class RngSoA(C.Structure):
+    """pbrt_rng_soa: PCG32 state and increment per ray (device arrays)."""
+    _fields_ = [("state", C.POINTER(C.c_uint64)), ("inc", C.POINTER(C.c_uint64))]
+
+
+class RadianceSoA(C.Structure):
+    """pbrt_radiance_soa: r, g, b are required; state, draws and rays may be NULL."""
+    _fields_ = [("r", C.POINTER(C.c_double)), ("g", C.POINTER(C.c_double)), ("b", C.POINTER(C.c_double)),
+                ("state", C.POINTER(C.c_uint64)), ("draws", C.POINTER(C.c_uint32)), ("rays", C.POINTER(C.c_uint32))]
+
+
+LI_SYMBOLS = ("pbrt_gpu_li_device",)
+
+
+def li_desc(max_depth=10, light_strategy=PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0,
+            integrator=PBRT_INTEGRATOR_PATH, reserved=0):
+    """LiDesc with render_desc's defaults."""
+    return LiDesc(integrator, max_depth, light_strategy, reserved, rr_threshold)
+
+
+def declare_li(L):
+    """ctypes prototype of pbrt_gpu_li_device. Apart from declare_query: a library of an
+    earlier build (PBRT_GPU_LIB) loads without this entry."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_li_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]

@@ -444,6 +444,63 @@ typedef struct pbrt_query_record {
 } pbrt_query_record;
 int pbrt_gpu_query_status(pbrt_gpu_ctx* ctx, pbrt_query_record* out);
 
+/* Integrator.Li over arrays that live on the device: ray i of the batch gets
+ * Path.Li(ray_i, scene, sampler, depth 0) (path.go:32-157), where the sampler is
+ * sampler.RandomSampler on the PCG32 stream (rng->state[i], rng->inc[i]): every
+ * Get1D / Get2D is a draw of that stream, in Path.Li's order, and no dimension
+ * is stratified. The ray's time is 0 (it reaches no draw and no output);
+ * rays->tmax may be NULL (+Inf). One kernel (k_li) runs the paths of the batch
+ * with the arithmetic of the render kernels (path_step), so a value is the bits
+ * a frame would add to its film for the same ray and stream.
+ *
+ * out->r/g/b receive Li's return value. The optional outputs (each may be NULL):
+ * state, the ray's PCG32 state after its path; draws, the number of PCG32 draws
+ * the path consumed (state is rng->state[i] advanced by draws steps); rays, the
+ * reference's ray counts of the path, closest-hit queries in the low 16 bits and
+ * visibility rays in the high 16. Li does not replace a NaN radiance: that is
+ * the Render loop's (integrator.go:256-262), and so the caller's.
+ *
+ * A ray on which the reference panics has r = g = b = 0, its optional outputs
+ * hold the values at the panic, and it is counted in the context's query record
+ * (pbrt_gpu_query_status) like a panicking ray of pbrt_gpu_intersect_device.
+ *
+ * Ordering and memory are pbrt_gpu_intersect_device's: every pointer is a device
+ * pointer to n elements; the call only enqueues on the context's stream, after
+ * everything already on it; n == 0 is PBRT_OK and launches nothing. The light
+ * distribution of desc->light_strategy is kept in a buffer of the query's own
+ * and uploaded only when the strategy differs from the one last uploaded, so a
+ * call in the steady state is one kernel launch: no allocation, copy or
+ * synchronisation.
+ *
+ * PBRT_E_INVALID, before any device call: a NULL context, desc, rays, ray
+ * pointer other than tmax, rng, rng->state, rng->inc, out, out->r/g/b;
+ * n > 2^31 - 1; max_depth < 1; reserved != 0; or a render in flight (left
+ * untouched). PBRT_E_UNSUPPORTED, with the reason in pbrt_gpu_last_error, where
+ * the kernel is not the reference: integrator other than PBRT_INTEGRATOR_PATH,
+ * max_depth > 2048, a scene with rough glass, an unknown light strategy, or a
+ * light distribution that mixes lights of pdf 0 with others. The reference's
+ * Power distribution is served: its entries are all 0 (SURVEY #28), so every
+ * picked light has pdf 0 and UniformSampleOneLight returns black after its one
+ * draw (integrator.go:56-58); k_li draws as it does, and no light reaches L. */
+typedef struct pbrt_li_desc {
+    int32_t integrator;      /* PBRT_INTEGRATOR_PATH                              */
+    int32_t max_depth;       /* 1..2048                                           */
+    int32_t light_strategy;  /* PBRT_LIGHT_STRATEGY_*                             */
+    int32_t reserved;        /* 0                                                 */
+    double  rr_threshold;
+} pbrt_li_desc;
+typedef struct pbrt_rng_soa {
+    const uint64_t *state, *inc;   /* PCG32 state and increment per ray          */
+} pbrt_rng_soa;
+typedef struct pbrt_radiance_soa {
+    double *r, *g, *b;       /* required                                          */
+    uint64_t *state;         /* optional                                          */
+    uint32_t *draws;         /* optional                                          */
+    uint32_t *rays;          /* optional: closest | shadow << 16                  */
+} pbrt_radiance_soa;
+int pbrt_gpu_li_device(pbrt_gpu_ctx* ctx, const pbrt_li_desc* desc, const pbrt_ray_soa* rays,
+                       const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out);
+
 /* Cancels the render in flight on ctx (from pbrt_gpu_render[_async[_into]]
  * entry until its pbrt_gpu_synchronize returns): the kernels poll a flag between
  * units of work (a pixel's chain, every 128 chain steps, a workgroup of paths),

@@ -376,6 +376,84 @@ func (p *Path) RenderFrame(ctx context.Context, scene pbrt.Scene, tileSize int64
 	return nil
 }
 
+// LiBatch is Path.Li (path.go:32-157) for a batch of the caller's own rays on the
+// GPU (Renderer.LiDevice): ray i samples with a sampler.RandomSampler on the PCG32
+// stream (state[i], inc[i]), depth 0. L[i] receives the radiance; a ray on which
+// the reference panics gets 0 and is counted in the returned record. It needs a
+// frame rendered on one device first (RenderFrame creates the device scene) and
+// keeps the integrator's maxDepth, rrThreshold and strategy. The arrays cross the
+// boundary in one C.malloc'd arena; the device buffers live for the call.
+func (p *Path) LiBatch(rays []*pbrt.Ray, state, inc []uint64, L [][3]float64) (QueryPanics, error) {
+	var none QueryPanics
+	n := len(rays)
+	if len(state) < n || len(inc) < n || len(L) < n {
+		return none, fmt.Errorf("pbrtgpu: %d rays need as many states, increments and results", n)
+	}
+	r, ok := p.renderer.(*Renderer)
+	if !ok || r == nil {
+		return none, errors.New("pbrtgpu: LiBatch needs a Path rendering on one device (call RenderFrame first)")
+	}
+	if n == 0 {
+		return none, nil
+	}
+	if n > maxBatchRays { // the arena's slices and its byte count stay in range
+		return none, fmt.Errorf("pbrtgpu: LiBatch takes at most %d rays a call", maxBatchRays)
+	}
+	a := newArena(n * (7*8 + 2*8 + 3*8))
+	defer a.free()
+	soa := packRays(a, rays)
+	cols := [7]*C.double{soa.ox, soa.oy, soa.oz, soa.dx, soa.dy, soa.dz, soa.tmax}
+	words := a.f64(2 * n) // state, inc: uint64 bit patterns moved as 8-byte words
+	su := (*[1 << 28]uint64)(unsafe.Pointer(&words[0]))[: 2*n : 2*n]
+	copy(su[:n], state[:n])
+	copy(su[n:], inc[:n])
+	res := a.f64(3 * n)
+	var bufs [12]*DeviceBuffer
+	defer func() {
+		for _, b := range bufs {
+			if b != nil {
+				b.Close()
+			}
+		}
+	}()
+	for k := range bufs {
+		b, err := r.NewDeviceBuffer(8 * n)
+		if err != nil {
+			return none, err
+		}
+		bufs[k] = b
+	}
+	for k := 0; k < 7; k++ {
+		if err := bufs[k].Upload(0, (*[1 << 28]float64)(unsafe.Pointer(cols[k]))[:n:n]); err != nil {
+			return none, err
+		}
+	}
+	for k := 0; k < 2; k++ {
+		if err := bufs[7+k].Upload(0, words[k*n:(k+1)*n]); err != nil {
+			return none, err
+		}
+	}
+	dr := DeviceRays{bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], bufs[5], bufs[6]}
+	out := DeviceRadiance{R: bufs[9], G: bufs[10], B: bufs[11]}
+	if err := r.LiDevice(dr, DeviceRNG{bufs[7], bufs[8]}, n, int32(p.rd.max_depth), float64(p.rd.rr_threshold),
+		int32(p.rd.light_strategy), out); err != nil {
+		return none, err
+	}
+	qp, err := r.QueryStatus()
+	if err != nil {
+		return qp, err
+	}
+	for k := 0; k < 3; k++ {
+		if err := bufs[9+k].Download(0, res[k*n:(k+1)*n]); err != nil {
+			return qp, err
+		}
+	}
+	for i := 0; i < n; i++ {
+		L[i] = [3]float64{res[i], res[n+i], res[2*n+i]}
+	}
+	return qp, nil
+}
+
 // Close releases the device scene.
 func (p *Path) Close() {
 	if p.renderer != nil {

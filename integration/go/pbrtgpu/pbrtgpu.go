@@ -491,6 +491,49 @@ func (r *Renderer) IntersectPDevice(rays DeviceRays, n int, occluded *DeviceBuff
 	return nil
 }
 
+// DeviceRNG holds the PCG32 stream of each ray of a LiDevice batch: State and Inc,
+// uint64 each.
+type DeviceRNG struct{ State, Inc *DeviceBuffer }
+
+// DeviceRadiance are the outputs of LiDevice: R, G, B (float64) are required;
+// State (uint64: the ray's stream after its path), Draws (uint32: the PCG32 draws
+// the path consumed) and Rays (uint32: closest | shadow << 16) may be nil.
+type DeviceRadiance struct{ R, G, B, State, Draws, Rays *DeviceBuffer }
+
+// LiDevice enqueues Path.Li(ray, scene, sampler, 0) for rays[0:n] on the
+// context's stream (pbrt_gpu_li_device): ray i samples with a RandomSampler on the
+// stream (State[i], Inc[i]). Nothing is copied or waited for; results are valid
+// after QueryStatus or a Download. A ray on which the reference panics has L = 0
+// and is counted in QueryStatus' record. DirectLighting, maxDepth > 2048 and
+// rough glass are refused with the reason.
+func (r *Renderer) LiDevice(rays DeviceRays, rng DeviceRNG, n int, maxDepth int32, rrThreshold float64,
+	strategy int32, out DeviceRadiance) error {
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return err
+	}
+	var gs C.pbrt_rng_soa
+	var rs C.pbrt_radiance_soa
+	p := [8]unsafe.Pointer{}
+	elem := [8]int{8, 8, 8, 8, 8, 8, 4, 4}
+	for k, d := range []*DeviceBuffer{rng.State, rng.Inc, out.R, out.G, out.B, out.State, out.Draws, out.Rays} {
+		if p[k], err = r.devPtr(d, n, elem[k], k > 4); err != nil {
+			return err
+		}
+	}
+	gs.state, gs.inc = (*C.uint64_t)(p[0]), (*C.uint64_t)(p[1])
+	rs.r, rs.g, rs.b = (*C.double)(p[2]), (*C.double)(p[3]), (*C.double)(p[4])
+	rs.state, rs.draws, rs.rays = (*C.uint64_t)(p[5]), (*C.uint32_t)(p[6]), (*C.uint32_t)(p[7])
+	var ld C.pbrt_li_desc
+	ld.integrator, ld.max_depth = C.PBRT_INTEGRATOR_PATH, C.int32_t(maxDepth)
+	ld.light_strategy, ld.reserved = C.int32_t(strategy), 0
+	ld.rr_threshold = C.double(rrThreshold)
+	if rc := C.pbrt_gpu_li_device(r.ctx, &ld, &soa, &gs, C.size_t(n), &rs); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_li_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
 // CameraRaysDevice writes the camera rays of the pixel window [x0, x1) x [y0, y1)
 // in raster order (pbrt_gpu_camera_rays_device), pFilm = pixel + filmOffset; an
 // IntersectDevice on them needs no host step in between.
