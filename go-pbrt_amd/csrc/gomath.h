@@ -172,6 +172,31 @@ GO_TRIG double sin(double x) {
     double y = (j == 1 || j == 2) ? detail::cos_poly(zz) : detail::sin_poly(z, zz);
     return sign ? -y : y;
 }
+// s = sin(x) and c = cos(x) above, bit for bit, from one evaluation: sin and cos
+// reduce the same |x| to the same (z, j), evaluate one polynomial each and differ
+// in which one and in the sign. Here one reduction and both polynomials serve the
+// pair, written as selects, so a 64-lane wave whose lanes fall into different
+// octants executes each polynomial once (sin + cos inline both polynomials and
+// the reduction twice). Every lane's s and c come from exactly the operations sin
+// and cos perform for its x; a non-finite x is reduced as 0 and its results are
+// replaced by the early returns of sin (x for ±0 and NaN, NaN for ±Inf) and cos.
+GO_TRIG void sincos(double x, double& s, double& c) {
+    const bool bad = is_nan(x) || is_inf(x);
+    uint64_t j;
+    const double z = detail::reduce(bad ? 0.0 : abs(x), j);
+    const bool upper = j > 3;   // both: j -= 4 and one sign flip
+    j = upper ? j - 4 : j;
+    const double zz = z * z;
+    const double sp = detail::sin_poly(z, zz), cp = detail::cos_poly(zz);
+    const bool swap = j == 1 || j == 2;
+    const double ys = swap ? cp : sp, yc = swap ? sp : cp;
+    const bool sign_s = (x < 0) != upper, sign_c = upper != (j > 1);
+    s = sign_s ? -ys : ys;
+    s = is_inf(x) ? nan() : s;
+    s = (x == 0 || is_nan(x)) ? x : s;
+    c = sign_c ? -yc : yc;
+    c = bad ? nan() : c;
+}
 // src/math/tan.go (host-side camera setup)
 GO_TRIG double tan(double x) {
     if (x == 0 || is_nan(x)) return x;
@@ -203,17 +228,30 @@ GO_HD double xatan(double x) {
          1.945506571482613964425e+02);
     return x * z + x;
 }
+// atan.go's satan: three ranges, each with its own xatan call there. Here the
+// range picks xatan's argument and the correction by selects and xatan (a rational
+// polynomial with an fp64 division) is evaluated once, so a wave whose lanes fall
+// into different ranges does not run it three times. Per lane the operations,
+// their operands and their order are those of the range's own line in atan.go:
+//   x <= 0.66            xatan(x)                                  (no division)
+//   x > Tan(3*Pi/8)      Pi/2 - xatan(1 / x) + Morebits
+//   otherwise (and NaN)  Pi/4 + xatan((x - 1) / (x + 1)) + 0.5 * Morebits
 GO_HD double satan(double x) {
     constexpr double Morebits = 6.123233995736765886130e-17;
-    if (x <= 0.66) return xatan(x);
-    if (x > 2.41421356237309504880) return kPi / 2 - xatan(1 / x) + Morebits;
-    return kPi / 4 + xatan((x - 1) / (x + 1)) + 0.5 * Morebits;
+    const bool lo = x <= 0.66, hi = x > 2.41421356237309504880;
+    double a = x;
+    if (!lo) a = (hi ? 1.0 : x - 1) / (hi ? x : x + 1);
+    const double r = xatan(a);
+    const double r_hi = kPi / 2 - r + Morebits, r_mid = kPi / 4 + r + 0.5 * Morebits;
+    return lo ? r : hi ? r_hi : r_mid;
 }
 }  // namespace detail
 
+// atan.go Atan: satan(x) or -satan(-x), one satan on the selected argument
 GO_HD double atan(double x) {
-    if (x == 0) return x;
-    return x > 0 ? detail::satan(x) : -detail::satan(-x);
+    const bool pos = x > 0;
+    const double r = detail::satan(pos ? x : -x);
+    return x == 0 ? x : pos ? r : -r;
 }
 // src/math/atan2.go
 GO_TRIG double atan2(double y, double x) {
@@ -230,14 +268,20 @@ GO_TRIG double atan2(double y, double x) {
     return q;
 }
 // src/math/asin.go
+// The two arms (Pi/2 - satan(t / x) above 0.7, satan(x / t) below) share one
+// division on selected operands and one satan; ±0 and |x| > 1 are replaced by
+// their early returns at the end (the square root of a negative number on the
+// way is a NaN nobody reads).
 GO_TRIG double asin(double x) {
-    if (x == 0) return x;
-    bool sign = false;
-    if (x < 0) { x = -x; sign = true; }
-    if (x > 1) return nan();
-    double t = __builtin_sqrt(1 - x * x);
-    t = (x > 0.7) ? kPi / 2 - detail::satan(t / x) : detail::satan(x / t);
-    return sign ? -t : t;
+    const bool sign = x < 0;
+    const double ax = sign ? -x : x;
+    const double t = __builtin_sqrt(1 - ax * ax);
+    const bool big = ax > 0.7;
+    double r = detail::satan((big ? t : ax) / (big ? ax : t));
+    r = big ? kPi / 2 - r : r;
+    r = sign ? -r : r;
+    r = ax > 1 ? nan() : r;
+    return x == 0 ? x : r;
 }
 GO_TRIG double acos(double x) { return kPi / 2 - asin(x); }
 GO_HD double sqrt(double x) { return __builtin_sqrt(x); }

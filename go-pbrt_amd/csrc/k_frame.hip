@@ -209,9 +209,12 @@ __global__ void k_panic_reduce(WaveBufs wb, int64_t slot_base, int64_t nslots_ba
 }
 
 
+// Two waves per SIMD by registers, as the kX build always had (243 VGPRs and 716 B/lane of scratch
+// with the branch-per-range trig): left to itself with the one-evaluation trig of gomath.h the
+// allocator takes 256 + 22 AccVGPRs and no scratch, one wave per SIMD. Bound: 256 VGPRs, 100 B/lane.
 template <bool kX>
-__global__ __launch_bounds__(kWave) void k_wf_primary(DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base,
-                                                      int64_t nb) {
+__global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(2, 8))) void k_wf_primary(
+    DevScene sc, RenderParams rp, WaveBufs wb, int64_t slot_base, int64_t nb) {
     __shared__ uint16_t stack_lds[64 * kStackStride];
     if (cancel_requested(sc, (blockIdx.x & 63) == 0)) return;
     stage_nodes(sc);

@@ -1145,19 +1145,19 @@ __device__ inline double bsdf_pdf(const BSDF& b, V3 woW, V3 wiW) {
     double pdf = 0 + lambert_pdf(wo, wi);
     return pdf / 1.0;
 }
-// sampling.go:173-198
-__device__ inline V2 concentric_sample_disk(V2 u) {
+// sampling.go:173-198. Its two exclusive branches (r = x, theta = Pi/4 * (y / x) and
+// r = y, theta = Pi/2 - Pi/4 * (x / y)) each hold one division: here one division
+// on selected operands, and one Sin/Cos evaluation (gomath::sincos) for the pair.
+__host__ __device__ inline V2 concentric_sample_disk(V2 u) {
     V2 uo{u.x * 2.0 - 1, u.y * 2.0 - 1};
-    if (uo.x == 0 && uo.y == 0) return V2{0, 0};
-    double theta, r;
-    if (gomath::abs(uo.x) > gomath::abs(uo.y)) {
-        r = uo.x;
-        theta = (gomath::kPi / 4.0) * (uo.y / uo.x);
-    } else {
-        r = uo.y;
-        theta = (gomath::kPi / 2.0) - (gomath::kPi / 4.0) * (uo.x / uo.y);
-    }
-    return V2{gomath::cos(theta) * r, gomath::sin(theta) * r};
+    const bool wide = gomath::abs(uo.x) > gomath::abs(uo.y);
+    const double r = wide ? uo.x : uo.y;
+    const double q = (gomath::kPi / 4.0) * ((wide ? uo.y : uo.x) / r);
+    const double theta = wide ? q : (gomath::kPi / 2.0) - q;
+    double s, c;
+    gomath::sincos(theta, s, c);
+    const bool centre = uo.x == 0 && uo.y == 0;
+    return V2{centre ? 0 : c * r, centre ? 0 : s * r};
 }
 // BSDF.SampleF (reflection.go:188-253) returning the LOCAL-frame wi (#7)
 __device__ inline Spec bsdf_sample_f(const BSDF& b, V3 woW, V2 u, V3& wi, double& pdf) {
@@ -1501,7 +1501,9 @@ __device__ inline void sphere_sample_at(const pbrt_shape_desc& s, const SI& ref,
         double z = 1.0 - 2.0 * u.x;
         double rr = gomath::sqrt(gomath::max(0, 1 - z * z));
         double ph = 2 * gomath::kPi * u.y;
-        V3 pobj = muls(V3{rr * gomath::cos(ph), rr * gomath::sin(ph), z}, s.radius);
+        double sin_ph, cos_ph;
+        gomath::sincos(ph, sin_ph, cos_ph);
+        V3 pobj = muls(V3{rr * cos_ph, rr * sin_ph, z}, s.radius);
         n = normalized(xf_normal(s.object_to_world.m_inv, pobj));
         if (s.reverse_orientation) n = muls(n, -1);
         pobj = muls(pobj, s.radius / dist(pobj, V3{0, 0, 0}));
@@ -1532,8 +1534,9 @@ __device__ inline void sphere_sample_at(const pbrt_shape_desc& s, const SI& ref,
     double cosa = (dc * dc + r2 - ds * ds) / (2.0 * dc * s.radius);
     double sina = gomath::sqrt(gomath::max(0, 1.0 - cosa * cosa));
     // SphericalDirectionXYZ (geometry.go:66-70) with -wcX, -wcY, -wc
-    V3 nw = (muls(muls(wcx, -1), sina * gomath::cos(phi)) + muls(muls(wcy, -1), sina * gomath::sin(phi))) +
-            muls(muls(wc, -1), cosa);
+    double sin_phi, cos_phi;
+    gomath::sincos(phi, sin_phi, cos_phi);
+    V3 nw = (muls(muls(wcx, -1), sina * cos_phi) + muls(muls(wcy, -1), sina * sin_phi)) + muls(muls(wc, -1), cosa);
     p = pc + muls(nw, s.radius);
     perr = muls(vabs(p), gomath::gamma(5.0));
     n = s.reverse_orientation ? muls(nw, -1) : nw;

@@ -2159,6 +2159,17 @@ __global__ void k_probe(int op, const double* __restrict__ in, int64_t n, int in
         }
         case PBRT_PROBE_NEXT_FLOAT_UP: o[0] = gomath::next_up(a[0]); break;
         case PBRT_PROBE_NEXT_FLOAT_DOWN: o[0] = gomath::next_down(a[0]); break;
+        case PBRT_PROBE_SINCOS: {
+            double s, c;
+            gomath::sincos(a[0], s, c);
+            o[0] = s; o[1] = c;
+            break;
+        }
+        case PBRT_PROBE_CONCENTRIC_DISK: {
+            V2 d = concentric_sample_disk(V2{a[0], a[1]});
+            o[0] = d.x; o[1] = d.y;
+            break;
+        }
         default: o[0] = gomath::nan();
     }
 }
@@ -2167,6 +2178,8 @@ __global__ void k_probe(int op, const double* __restrict__ in, int64_t n, int in
 extern "C" int pbrt_gpu_probe(int device, int op, const double* in, size_t n, int in_stride, double* out,
                               int out_stride) {
     if (!in || !out || in_stride <= 0 || out_stride <= 0) return PBRT_E_INVALID;
+    if ((op == PBRT_PROBE_SINCOS || op == PBRT_PROBE_CONCENTRIC_DISK) && out_stride < 2) return PBRT_E_INVALID;
+    if (op == PBRT_PROBE_CONCENTRIC_DISK && in_stride < 2) return PBRT_E_INVALID;
     if (n == 0) return PBRT_OK;
     if (device >= 0 && hipSetDevice(device) != hipSuccess) return PBRT_E_HIP;
     DevBuf<double> in_buf, out_buf;

@@ -69,6 +69,7 @@ def lib():
     if hasattr(L, "pbrt_gpu_li_device"):   # (a library of an earlier build, PBRT_GPU_LIB, has no such entry)
         abi.declare_li(L)
     abi.declare_launch_log(L)
+    abi.declare_probe(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
     L.pbrt_gpu_tile_ticks.argtypes = [C.c_void_p, P(C.c_uint32), i64, P(i64)]
     L.pbrt_gpu_tile_ticks.restype = i64

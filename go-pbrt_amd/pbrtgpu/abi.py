@@ -423,3 +423,38 @@ def declare_li(L):
     earlier build (PBRT_GPU_LIB) loads without this entry."""
     P, vp = C.POINTER, C.c_void_p
     L.pbrt_gpu_li_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]
+
+
+# pbrt_gpu_probe ops (include/pbrt_diag.h): one device function on a batch of inputs
+PBRT_PROBE_SIN = 1
+PBRT_PROBE_COS = 2
+PBRT_PROBE_TAN = 3
+PBRT_PROBE_ATAN = 4
+PBRT_PROBE_ATAN2 = 5
+PBRT_PROBE_ASIN = 6
+PBRT_PROBE_ACOS = 7
+PBRT_PROBE_SQRT = 8
+PBRT_PROBE_DIV = 9
+PBRT_PROBE_NEXTAFTER = 10
+PBRT_PROBE_MAX = 11
+PBRT_PROBE_MIN = 12
+PBRT_PROBE_OFFSET_RAY_ORIGIN = 13
+PBRT_PROBE_EFLOAT_ADD = 14
+PBRT_PROBE_TRANSFORM_RAY = 15
+PBRT_PROBE_SPAWN_RAY_TO = 16
+PBRT_PROBE_PCG = 17
+PBRT_PROBE_NEXT_FLOAT_UP = 18
+PBRT_PROBE_NEXT_FLOAT_DOWN = 19
+PBRT_PROBE_MIN_NONAN = 20
+PBRT_PROBE_MAX_NONAN = 21
+PBRT_PROBE_EFLOAT_MUL = 22
+PBRT_PROBE_EFLOAT_DIV = 23
+PBRT_PROBE_SINCOS = 24            # in a -> Sin(a), Cos(a) from one evaluation
+PBRT_PROBE_CONCENTRIC_DISK = 25   # in u[2] -> ConcentricSampleDisk(u)[2]
+
+
+def declare_probe(L):
+    """ctypes prototype of pbrt_gpu_probe."""
+    P = C.POINTER
+    L.pbrt_gpu_probe.argtypes = [C.c_int, C.c_int, P(C.c_double), C.c_size_t, C.c_int, P(C.c_double), C.c_int]
+    L.pbrt_gpu_probe.restype = C.c_int

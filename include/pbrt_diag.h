@@ -39,7 +39,9 @@ enum {
     PBRT_PROBE_MIN_NONAN = 20,         /* in x, y (not NaN) -> device min used by EFloat */
     PBRT_PROBE_MAX_NONAN = 21,         /* in x, y (not NaN) -> device max used by EFloat */
     PBRT_PROBE_EFLOAT_MUL = 22,        /* in v1 e1 v2 e2 -> value low high panic */
-    PBRT_PROBE_EFLOAT_DIV = 23         /* in v1 e1 v2 e2 -> value low high panic */
+    PBRT_PROBE_EFLOAT_DIV = 23,        /* in v1 e1 v2 e2 -> value low high panic */
+    PBRT_PROBE_SINCOS = 24,            /* in a -> Sin(a), Cos(a) from one evaluation (gomath::sincos) */
+    PBRT_PROBE_CONCENTRIC_DISK = 25    /* in u[2] -> ConcentricSampleDisk(u)[2] (sampling.go:173-198) */
 };
 
 /* Host instantiation of the float64 vector / spectrum operations the kernels

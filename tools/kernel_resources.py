@@ -13,11 +13,17 @@ import sys
 
 
 def demangle_short(sym):
-    m = re.search(r"_GLOBAL__N_1\d+(k_\w+?)(I.*?)?E?Ev", sym) or re.search(r"(k_\w+)", sym)
-    name = m.group(1) if m else sym
-    targs = re.findall(r"L([ib])(\d+)E", sym[:200])
-    if targs:
-        name += "<" + ", ".join(("true" if v == "1" else "false") if t == "b" else v for t, v in targs) + ">"
+    """The launch log's spelling of a kernel symbol: k_name<int and bool template arguments>
+    (Itanium: <length>k_name, then I L<type>[n]<value>E ... E for the arguments)."""
+    m = re.search(r"(\d+)(k_\w+)", re.sub(r"\d*_GLOBAL__N_1", "", sym))
+    if not m:
+        return sym
+    n = int(m.group(1))
+    name, rest = m.group(2)[:n], m.group(2)[n:]
+    t = re.match(r"I((?:L[ib]n?\d+E)+)E", rest)
+    if t:
+        name += "<" + ", ".join(("true" if v == "1" else "false") if ty == "b" else ("-" + v if neg else v)
+                                for ty, neg, v in re.findall(r"L([ib])(n?)(\d+)E", t.group(1))) + ">"
     return name
 
 
