@@ -53,6 +53,8 @@ struct Knobs {
     int cull_group = 4;        // PBRT_CULL_GROUP: leaves per culling group
     int cull_min = 2;          // PBRT_CULL_MIN
     bool cull_groups = true;   // PBRT_CULL_GROUPS=0
+    bool film_add_lds = true;  // PBRT_FILM_ADD=direct: pbrt_gpu_film_add_device's tile films by the direct gather
+                               // (k_film_add_tiles<false>) where the LDS-staged one would run
     static Knobs from_env() {
         Knobs k;
         auto ival = [](const char* n, int& out) { if (const char* e = getenv(n)) out = atoi(e); };
@@ -94,6 +96,7 @@ struct Knobs {
         int cg = 1;
         ival("PBRT_CULL_GROUPS", cg);
         k.cull_groups = cg != 0;
+        if (const char* e = getenv("PBRT_FILM_ADD")) k.film_add_lds = std::strcmp(e, "direct") != 0;
         return k;
     }
 };

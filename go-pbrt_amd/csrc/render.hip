@@ -48,6 +48,7 @@
 #include "knobs.h"
 #include "mesh_bvh.h"
 #include "li_query.h"
+#include "film_query.h"
 #include "query_buffers.h"
 #include "render_kernels.h"
 #include "scene_tables.h"
@@ -261,6 +262,8 @@ struct pbrt_gpu_ctx {
         pbrt_distribution_desc host_dist;
         int strategy = 0;   // the strategy d_dist holds (0: none yet)
     } li;
+    // pbrt_gpu_film_add_device: the tile films of a call's tile range (grown on demand)
+    DevBuf<double> d_fq_films;
     // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
     // (cleared by render_enqueue) and those outside a frame (LBVH build, queries)
     LaunchLog log_frame, log_aux;
@@ -1965,6 +1968,95 @@ int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_so
     return PBRT_OK;
 }
 
+// ---- a frame from public pieces (k_film_q.hip). The layout, the checks and the refusals: film_query.h.
+// The RenderParams the film kernels' tile_bounds / film_tile_bounds read, for a tile size of the caller's.
+static RenderParams frame_params(const pbrt_gpu_ctx* c, const pbrtfilm::Layout& l) {
+    const pbrt_film_desc& f = c->host_scene.film;
+    RenderParams rp{};
+    rp.film_min_x = l.min_x;
+    rp.film_min_y = l.min_y;
+    rp.film_w = l.w;
+    rp.film_h = l.h;
+    rp.tile_size = l.ts;
+    rp.ntx = l.ntx;
+    rp.nty = l.nty;
+    rp.tile_stride = 1;
+    rp.slot_w = pbrtfilm::slot_extent(l.ts, f.filter_radius_x);
+    rp.slot_h = pbrtfilm::slot_extent(l.ts, f.filter_radius_y);
+    return rp;
+}
+
+int64_t pbrt_gpu_frame_count(const pbrt_gpu_ctx* c, const pbrt_frame_desc* d) {
+    const char* why = "";
+    int64_t n = 0;
+    if (pbrtfilm::check_frame(c != nullptr, c ? &c->host_scene.film : nullptr, d, PBRT_FILM_ADD_CLEAR, false, &n, &why))
+        return -PBRT_E_INVALID;
+    return n;
+}
+
+int pbrt_gpu_frame_samples_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, const pbrt_frame_samples_soa* out) {
+    const char* why = "";
+    int64_t n = 0;
+    const pbrt_film_desc* f = c ? &c->host_scene.film : nullptr;
+    if (int rc = pbrtfilm::check_frame(c != nullptr, f, d, 0, c && query_blocked(c), &n, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtfilm::check_samples_out(out, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtfilm::check_frame_supported(*f, *d, false, &why)) return set_err(c, rc, why);
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
+    launch_k(c, k_frame_samples, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0, c->stream,
+             c->d_camera.get(), l, pbrtfilm::pixels_before(l, d->tile_begin), (int)d->ns, n, *out);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+int pbrt_gpu_film_add_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, const pbrt_film_samples_soa* in,
+                             double* film_device) {
+    const char* why = "";
+    int64_t n = 0;
+    const pbrt_film_desc* f = c ? &c->host_scene.film : nullptr;
+    if (int rc = pbrtfilm::check_frame(c != nullptr, f, d, PBRT_FILM_ADD_CLEAR, c && query_blocked(c), &n, &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtfilm::check_film_in(in, film_device, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtfilm::check_frame_supported(*f, *d, true, &why)) return set_err(c, rc, why);
+    const bool clear = (d->flags & PBRT_FILM_ADD_CLEAR) != 0;
+    if (n == 0 && !clear) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
+    const RenderParams rp = frame_params(c, l);
+    const int64_t nt = d->tile_end - d->tile_begin;
+    if (nt > 0) {
+        if (int rc = c->d_fq_films.ensure(c, pbrtfilm::scratch_doubles(*f, d->tile_size, d->tile_begin, d->tile_end)))
+            return rc;
+        launch_k(c, pbrtfilm::lds_gather(c->knobs.film_add_lds, *f, d->tile_size) ? k_film_add_tiles<true> : k_film_add_tiles<false>,
+                 dim3((unsigned)nt), dim3(kFilmThreads), 0, c->stream, c->d_film.get(), rp, l, (int64_t)d->tile_begin,
+                 (int)d->ns, *in, c->d_fq_films.get());
+    }
+    const pbrtfilm::Rows rows = pbrtfilm::rows_touched(l, *f, d->tile_begin, d->tile_end, clear);
+    const int64_t npx = (rows.y1 - rows.y0) * l.w;
+    if (npx > 0)
+        launch_k(c, k_film_add_merge, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film.get(), rp,
+                 (int64_t)d->tile_begin, (int64_t)d->tile_end, rows.y0, rows.y1 - rows.y0, clear ? 1 : 0,
+                 (const double*)c->d_fq_films.get(), film_device);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+int pbrt_gpu_film_rgba8_device(pbrt_gpu_ctx* c, const double* film_device, int64_t w, int64_t h, uint8_t* rgba_device) {
+    const char* why = "";
+    if (int rc = pbrtfilm::check_rgba8(c != nullptr, film_device, w, h, rgba_device, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t n = w * h;
+    launch_k(c, k_film_rgba8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, film_device, n,
+             (uint32_t*)rgba_device);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+// (diagnostics) the capacity of film_add's scratch buffer in bytes: it changes only when the buffer is allocated anew
+size_t pbrt_gpu_film_scratch_bytes(const pbrt_gpu_ctx* c) { return c ? c->d_fq_films.cap() * sizeof(double) : 0; }
+
 int pbrt_gpu_query_status(pbrt_gpu_ctx* c, pbrt_query_record* out) {
     if (!c) return PBRT_E_INVALID;
     if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
@@ -2336,6 +2428,12 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_query_hit_staged<true>),
     PBRT_KERNEL_NAME(k_query_camera),
     PBRT_KERNEL_NAME(k_probe),
+    // k_film_q.hip
+    PBRT_KERNEL_NAME(k_frame_samples),
+    PBRT_KERNEL_NAME(k_film_add_tiles<false>),
+    PBRT_KERNEL_NAME(k_film_add_tiles<true>),
+    PBRT_KERNEL_NAME(k_film_add_merge),
+    PBRT_KERNEL_NAME(k_film_rgba8),
 };
 
 template <class F>

@@ -3,6 +3,7 @@
 // translation unit; the launch goes through the host stub that unit emits.
 #pragma once
 
+#include "film_query.h"
 #include "group.h"
 #include "render_common.h"
 
@@ -63,5 +64,11 @@ __global__ void k_query_camera(const pbrt_camera_desc* __restrict__ cam, pbrt_ca
 // batched Integrator.Li over device arrays (pbrt_gpu_li_device): k_li.hip
 template <bool kX, int kDepth>
 __global__ void k_li(DevScene sc, int max_depth, double rr_threshold, int64_t n, pbrt_ray_soa rays, pbrt_rng_soa rng, pbrt_radiance_soa out, QueryRec* __restrict__ rec);
+// a frame from public pieces (pbrt_gpu_frame_samples_device, pbrt_gpu_film_add_device, pbrt_gpu_film_rgba8_device): k_film_q.hip
+__global__ void k_frame_samples(const pbrt_camera_desc* __restrict__ cam, pbrtfilm::Layout lay, int64_t px_begin, int ns, int64_t n, pbrt_frame_samples_soa out);
+template <bool kLds>
+__global__ void k_film_add_tiles(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, pbrtfilm::Layout lay, int64_t tile_begin, int ns, pbrt_film_samples_soa in, double* __restrict__ films);
+__global__ void k_film_add_merge(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, int64_t tile_begin, int64_t tile_end, int64_t row0, int64_t rows, int clear, const double* __restrict__ films, double* __restrict__ out);
+__global__ void k_film_rgba8(const double* __restrict__ film, int64_t n, uint32_t* __restrict__ rgba);
 
 }  // namespace pbrtk

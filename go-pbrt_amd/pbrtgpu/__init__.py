@@ -68,6 +68,8 @@ def lib():
     abi.declare_query(L)
     if hasattr(L, "pbrt_gpu_li_device"):   # (a library of an earlier build, PBRT_GPU_LIB, has no such entry)
         abi.declare_li(L)
+    if hasattr(L, "pbrt_gpu_film_add_device"):
+        abi.declare_frame(L)
     abi.declare_launch_log(L)
     abi.declare_probe(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
@@ -456,6 +458,12 @@ HIT_DTYPES = {"hit": np.uint8, "t_max": np.float64, "prim": np.int32, "px": np.f
 RNG_KEYS = ("state", "inc")
 LI_DTYPES = {"r": np.float64, "g": np.float64, "b": np.float64, "state": np.uint64, "draws": np.uint32,
              "rays": np.uint32}
+# frame_samples' outputs (tmax, px, py optional) and film_add's inputs
+SAMPLE_DTYPES = {**{k: np.float64 for k in RAY_KEYS + ("tmax", "pfilm_x", "pfilm_y")}, "state": np.uint64,
+                 "inc": np.uint64, "px": np.int32, "py": np.int32}
+SAMPLE_REQUIRED = RAY_KEYS + ("pfilm_x", "pfilm_y", "state", "inc")
+FILM_KEYS = ("pfilm_x", "pfilm_y", "r", "g", "b")
+FRAME_BYTES_PER_SAMPLE = 8 * (len(SAMPLE_REQUIRED) + 3)   # a composed frame's arrays: 104 B (render_samples)
 
 
 class DeviceBuffer:
@@ -822,6 +830,146 @@ class Renderer:
     def last_error(self):
         """pbrt_gpu_last_error: the reason of the context's last refusal."""
         return lib().pbrt_gpu_last_error(self.h).decode()
+
+    # ---- a frame from public pieces: samples, li_device, film_add, film_rgba8
+    def num_tiles(self, tile_size=16):
+        """Tiles of the film's cropped bounds at tile_size (integrator.go:316-325)."""
+        return ((self.w + tile_size - 1) // tile_size) * ((self.hgt + tile_size - 1) // tile_size)
+
+    def _frame_desc(self, what, ns, tile_begin, tile_end, tile_size, flags=0):
+        """(desc, element count) of a tile range; raises where pbrt_gpu_frame_count refuses the desc.
+        (A tile size or ns beyond what the kernels handle counts 0 here: the call itself then
+        returns PBRT_E_UNSUPPORTED with the reason.)"""
+        if tile_end is None:
+            tile_end = self.num_tiles(tile_size) if tile_size >= 1 else 0
+        d = abi.frame_desc(tile_size, ns, tile_begin, tile_end, flags)
+        n = lib().pbrt_gpu_frame_count(self.h, C.byref(d))
+        if n < 0:
+            raise PbrtError(-n, f"{what}: tile_size {tile_size}, ns {ns}, tiles [{tile_begin}, {tile_end}): "
+                                "outside the film's tiles, or more than 2^31 - 1 samples")
+        return d, n
+
+    def frame_count(self, ns, tile_begin=0, tile_end=None, tile_size=16):
+        """pbrt_gpu_frame_count: the elements of the tile range [tile_begin, tile_end) (None: to the
+        last tile) in the frame layout, ns samples per pixel."""
+        return self._frame_desc("frame_count", ns, tile_begin, tile_end, tile_size)[1]
+
+    def frame_samples(self, out, ns, tile_begin=0, tile_end=None, tile_size=16):
+        """pbrt_gpu_frame_samples_device: the traced samples (k = 1 .. ns, spp = ns + 1) of a
+        THROUGHPUT render with n_dims = 0 over a tile range, in the frame layout, into the
+        buffers of out: ox..dz, pfilm_x, pfilm_y (float64), state, inc (uint64), and optionally
+        tmax (float64), px, py (int32). Enqueue only. Returns the status."""
+        unknown = set(out) - set(SAMPLE_DTYPES)
+        missing = [k for k in SAMPLE_REQUIRED if out.get(k) is None]
+        if unknown or missing:
+            raise PbrtError(abi.PBRT_E_INVALID, f"frame_samples: unknown {sorted(unknown)}, missing {missing}")
+        d, n = self._frame_desc("frame_samples", ns, tile_begin, tile_end, tile_size)
+        ob = [(k, out[k], dt) for k, dt in SAMPLE_DTYPES.items() if out.get(k) is not None]
+        check_buffers(self, n, ob)
+        os_ = _soa(abi.FrameSamplesSoA, ob)
+        return lib().pbrt_gpu_frame_samples_device(self.h, C.byref(d), C.byref(os_))
+
+    def _film_ptr(self, what, film, elements, dtype):
+        """The device address of a film argument: a DeviceBuffer of this context (checked against
+        the elements the call touches) or an address (a tensor's data_ptr(), film_device_ptr())."""
+        if isinstance(film, DeviceBuffer):
+            check_buffers(self, elements, [(what, film, dtype)])
+            return film.ptr
+        if not isinstance(film, (int, np.integer)) or not film:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{what}: a DeviceBuffer or a device address")
+        return int(film)
+
+    def film_add(self, samples, ns, film, tile_begin=0, tile_end=None, tile_size=16, clear=False):
+        """pbrt_gpu_film_add_device: adds the film of the samples of a tile range (pfilm_x,
+        pfilm_y, r, g, b: float64 buffers in the frame layout, ns per pixel) to film, the (H, W,
+        3) XYZ film on the device (a float64 DeviceBuffer or a device address); clear zeroes it
+        first. Ascending ranges over several calls give the bits of one call. Enqueue only.
+        Returns the status (PBRT_E_UNSUPPORTED: last_error() says why)."""
+        unknown = set(samples) - set(FILM_KEYS)
+        missing = [k for k in FILM_KEYS if samples.get(k) is None]
+        if unknown or missing:
+            raise PbrtError(abi.PBRT_E_INVALID, f"film_add: unknown {sorted(unknown)}, missing {missing}")
+        d, n = self._frame_desc("film_add", ns, tile_begin, tile_end, tile_size,
+                                abi.PBRT_FILM_ADD_CLEAR if clear else 0)
+        sb = [(k, samples[k], np.float64) for k in FILM_KEYS]
+        check_buffers(self, n, sb)
+        ptr = self._film_ptr("film", film, self.hgt * self.w * 3, np.float64)
+        ss = _soa(abi.FilmSamplesSoA, sb)
+        return lib().pbrt_gpu_film_add_device(self.h, C.byref(d), C.byref(ss), C.c_void_p(ptr))
+
+    def film_rgba8(self, film, rgba=None, w=None, h=None):
+        """pbrt_gpu_film_rgba8_device: film_to_rgba8's bytes of a device film of w x h pixels (None:
+        the context's film size) into rgba, a uint8 DeviceBuffer of w * h * 4 (None: a new one) or a
+        4-byte aligned device address. Enqueue only. Returns rgba."""
+        w, h = self.w if w is None else int(w), self.hgt if h is None else int(h)
+        if w <= 0 or h <= 0 or w * h > 2**31 - 1:
+            raise PbrtError(abi.PBRT_E_INVALID, f"film_rgba8: {w} x {h} pixels")
+        if rgba is None:
+            rgba = self.buffer(w * h * 4, np.uint8)
+        fptr = self._film_ptr("film", film, w * h * 3, np.float64)
+        rptr = self._film_ptr("rgba", rgba, w * h * 4, np.uint8)
+        self._check(lib().pbrt_gpu_film_rgba8_device(self.h, C.c_void_p(fptr), w, h, C.c_void_p(rptr)))
+        return rgba
+
+    def film_scratch_bytes(self):
+        """pbrt_gpu_film_scratch_bytes: the size of film_add's scratch buffer (it changes only when
+        a call allocates)."""
+        return lib().pbrt_gpu_film_scratch_bytes(self.h)
+
+    def frame_ranges(self, ns, tile_size=16, budget_bytes=1 << 30):
+        """Ascending tile ranges [(begin, end, elements)] over the whole film whose sample arrays
+        (FRAME_BYTES_PER_SAMPLE bytes a sample) fit budget_bytes, at least one tile each."""
+        nt = self.num_tiles(tile_size)
+        per = max(1, int(budget_bytes) // (FRAME_BYTES_PER_SAMPLE * ns * tile_size * tile_size))
+        return [(b, min(b + per, nt), self.frame_count(ns, b, min(b + per, nt), tile_size)) for b in range(0, nt, per)]
+
+    def render_samples(self, spp, max_depth=10, light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0,
+                       tile_size=16, budget_bytes=1 << 30, film=None, count_rays=False):
+        """A THROUGHPUT frame with n_dims = 0 composed of the public stages: per ascending tile
+        range sized to budget_bytes, frame_samples, li_device and film_add, all on the device; the
+        film is pbrt_gpu_render's, bit for bit. film: a float64 DeviceBuffer of H * W * 3 to
+        compose into (None: one of the call's own). Returns (the (H, W, 3) film, info): info has
+        the ranges, the samples and, with count_rays, the reference's closest and shadow ray
+        counts (which downloads 4 bytes per sample). Raises PbrtError on a refusal and
+        PBRT_E_REF_PANIC when the reference panics on a path."""
+        ns = int(spp) - 1
+        if ns < 1:
+            raise PbrtError(abi.PBRT_E_INVALID, "render_samples: spp >= 2 (sample 0 of a pixel is never traced)")
+        ranges = self.frame_ranges(ns, tile_size, budget_bytes)
+        cap = max(n for _, _, n in ranges)
+        own = []
+        try:
+            if film is None:
+                film = self.buffer(self.hgt * self.w * 3)
+                own.append(film)
+            sb = {k: self.buffer(cap, SAMPLE_DTYPES[k]) for k in SAMPLE_REQUIRED}
+            ob = {k: self.buffer(cap) for k in ("r", "g", "b")}
+            if count_rays:
+                ob["rays"] = self.buffer(cap, np.uint32)
+            own += list(sb.values()) + list(ob.values())
+            rays = {k: sb[k] for k in RAY_KEYS}
+            rng = {k: sb[k] for k in RNG_KEYS}
+            fs = dict(pfilm_x=sb["pfilm_x"], pfilm_y=sb["pfilm_y"], r=ob["r"], g=ob["g"], b=ob["b"])
+            closest = shadow = 0
+            for i, (b, e, n) in enumerate(ranges):
+                self._check(self.frame_samples(sb, ns, b, e, tile_size))
+                self._check(self.li_device(rays, rng, n, ob, max_depth, light_strategy, rr_threshold))
+                self._check(self.film_add(fs, ns, film, b, e, tile_size, clear=i == 0))
+                if count_rays:
+                    v = ob["rays"].download()[:n]
+                    closest += int((v & 0xFFFF).sum())
+                    shadow += int((v >> 16).sum())
+            rc, rec = self.query_status()
+            if rc:
+                raise PbrtError(rc, self.last_error(), rec)
+            out = film.download()[:self.hgt * self.w * 3].reshape(self.hgt, self.w, 3)
+        finally:
+            for b in own:
+                b.close()
+        info = {"ranges": len(ranges), "samples": sum(n for _, _, n in ranges)}
+        if count_rays:
+            info.update(closest_rays=closest, shadow_rays=shadow)
+        return out, info
 
     def radiance(self, rays, state, inc, **desc):
         """Path.Li of host rays: rays is (n, 6) [ox, oy, oz, dx, dy, dz] or (n, 7) with tmax,

@@ -425,6 +425,48 @@ def declare_li(L):
     L.pbrt_gpu_li_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]
 
 
+# --------------------------------- a frame from public pieces (include/pbrt_gpu.h)
+PBRT_FILM_ADD_CLEAR = 1
+
+
+class FrameDesc(C.Structure):
+    """pbrt_frame_desc: a tile range of the frame layout."""
+    _fields_ = [("tile_size", C.c_int32), ("ns", C.c_int32), ("tile_begin", C.c_int64), ("tile_end", C.c_int64),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class FrameSamplesSoA(C.Structure):
+    """pbrt_frame_samples_soa: what pbrt_gpu_frame_samples_device writes; tmax, px, py may be NULL."""
+    _fields_ = ([(n, C.POINTER(C.c_double)) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "tmax", "pfilm_x", "pfilm_y")]
+                + [("state", C.POINTER(C.c_uint64)), ("inc", C.POINTER(C.c_uint64)),
+                   ("px", C.POINTER(C.c_int32)), ("py", C.POINTER(C.c_int32))])
+
+
+class FilmSamplesSoA(C.Structure):
+    """pbrt_film_samples_soa: what pbrt_gpu_film_add_device reads."""
+    _fields_ = [(n, C.POINTER(C.c_double)) for n in ("pfilm_x", "pfilm_y", "r", "g", "b")]
+
+
+FRAME_SYMBOLS = ("pbrt_gpu_frame_count", "pbrt_gpu_frame_samples_device", "pbrt_gpu_film_add_device",
+                 "pbrt_gpu_film_rgba8_device", "pbrt_gpu_film_scratch_bytes")
+
+
+def frame_desc(tile_size, ns, tile_begin, tile_end, flags=0, reserved=0):
+    return FrameDesc(tile_size, ns, tile_begin, tile_end, flags, reserved)
+
+
+def declare_frame(L):
+    """ctypes prototypes of the frame calls (apart, like declare_li: an earlier build has none)."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_frame_count.argtypes = [vp, P(FrameDesc)]
+    L.pbrt_gpu_frame_count.restype = C.c_int64
+    L.pbrt_gpu_frame_samples_device.argtypes = [vp, P(FrameDesc), P(FrameSamplesSoA)]
+    L.pbrt_gpu_film_add_device.argtypes = [vp, P(FrameDesc), P(FilmSamplesSoA), vp]
+    L.pbrt_gpu_film_rgba8_device.argtypes = [vp, vp, C.c_int64, C.c_int64, vp]
+    L.pbrt_gpu_film_scratch_bytes.argtypes = [vp]
+    L.pbrt_gpu_film_scratch_bytes.restype = C.c_size_t
+
+
 # pbrt_gpu_probe ops (include/pbrt_diag.h): one device function on a batch of inputs
 PBRT_PROBE_SIN = 1
 PBRT_PROBE_COS = 2

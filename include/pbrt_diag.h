@@ -151,6 +151,12 @@ int pbrt_gpu_kernel_names(const char** out, int n);
 const char* pbrt_diag_kernel_choice(const char* family, const int* args, int n);
 /* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */
 int64_t pbrt_gpu_lds_per_block(struct pbrt_gpu_ctx* ctx);
+/* Bytes of the scratch buffer in which pbrt_gpu_film_add_device keeps the tile
+ * films of a call's range: the one allocation of the frame calls. It is
+ * allocated anew only when a call needs more than it holds, and then at that
+ * call's size, so a value that stays the same across calls shows that they
+ * allocated nothing. 0 before the first film_add. */
+size_t pbrt_gpu_film_scratch_bytes(const struct pbrt_gpu_ctx* ctx);
 
 /* pbrt_gpu_intersect_device / pbrt_gpu_intersect_p_device (pbrt_gpu.h: the same
  * buffers, record and status) through the LDS-staged walks of the render

@@ -501,6 +501,110 @@ typedef struct pbrt_radiance_soa {
 int pbrt_gpu_li_device(pbrt_gpu_ctx* ctx, const pbrt_li_desc* desc, const pbrt_ray_soa* rays,
                        const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out);
 
+/* ---------------------------------------------- a frame from public pieces
+ * Three enqueue-only calls that, with pbrt_gpu_li_device between the first two,
+ * build a frame on the device: samples, Li, film, RGBA8. The composed film is a
+ * THROUGHPUT render's with n_dims = 0, bit for bit; a caller may replace any
+ * stage (their own camera, their own treatment of the radiances) and keep the
+ * others. Ordering and memory are pbrt_gpu_intersect_device's: every pointer is
+ * a device pointer, a call only enqueues on the context's stream after
+ * everything already on it, and it neither synchronises nor copies.
+ * pbrt_gpu_film_add_device keeps the tile films of a range in a scratch buffer
+ * the context owns, which grows on demand (the one allocation of these calls: a
+ * second call at the same or a smaller size allocates nothing) and is freed
+ * with the context.
+ *
+ * THE FRAME LAYOUT, shared by frame_samples and film_add. Tiles in index order
+ * over the film's cropped pixel bounds at tile_size (integrator.go:316-325:
+ * tile t covers x0 = crop_min_x + (t % ntx) * tile_size .. min(x0 + tile_size,
+ * crop_max_x), likewise y with t / ntx); pixels row-major inside their tile;
+ * ns consecutive samples per pixel; dense, no padding. With W the crop width,
+ * ts the tile size and h(ty) = min(ts, H - ty * ts) the height of tile row ty,
+ * ty * ts * W + tx * ts * h(ty) pixels come before tile (tx, ty). A call covers
+ * the tiles [tile_begin, tile_end); element 0 of every array is the first
+ * sample of tile_begin's first pixel. pbrt_gpu_frame_count returns the element
+ * count of the range (what every array must hold), or -PBRT_E_INVALID where
+ * the call itself would return PBRT_E_INVALID for the desc.
+ *
+ * PBRT_E_INVALID of the frame calls, before any device call: a NULL context,
+ * desc or required pointer; tile_size < 1; ns < 1; flags other than
+ * PBRT_FILM_ADD_CLEAR; reserved != 0; a tile range outside 0 <= tile_begin <=
+ * tile_end <= ntx * nty; more than 2^31 - 1 elements; or a render in flight
+ * (left untouched). An empty range (tile_begin == tile_end) is PBRT_OK and
+ * launches nothing, except that film_add with PBRT_FILM_ADD_CLEAR still clears.
+ * PBRT_E_UNSUPPORTED, with the reason in pbrt_gpu_last_error: tile_size > 256 or
+ * ns > 2^20 - 1. */
+enum { PBRT_FILM_ADD_CLEAR = 1 };   /* film_add: zero the film first            */
+typedef struct pbrt_frame_desc {
+    int32_t tile_size;       /* 1..256                                            */
+    int32_t ns;              /* samples per pixel in the arrays, 1..2^20 - 1      */
+    int64_t tile_begin, tile_end;
+    int32_t flags;           /* film_add: PBRT_FILM_ADD_CLEAR; else 0             */
+    int32_t reserved;        /* 0                                                 */
+} pbrt_frame_desc;
+int64_t pbrt_gpu_frame_count(const pbrt_gpu_ctx* ctx, const pbrt_frame_desc* desc);
+
+/* The traced samples of a THROUGHPUT render with n_dims = 0 (sampler.RandomSampler
+ * semantics) and spp = ns + 1, in the frame layout: sample 0 of a pixel is never
+ * traced (sampler.go:29-34), so position j of a pixel holds its sample k = j + 1.
+ * Sample k of pixel pi of tile t starts at the PCG32 state mb_state(t, pi, k)
+ * (three rounds of splitmix64: csrc/pbrt_path.h) on the stream inc = 2 t + 1,
+ * draws pFilm x, pFilm y, pLens x, pLens y and the time (sampler.go:75-80), and
+ * its ray is PerspectiveCamera.GenerateRay of those (pbrt_gpu_camera_rays_device's
+ * arithmetic). Written per sample: the ray (tmax may be NULL; it is +Inf);
+ * pfilm_x, pfilm_y, the absolute raster position (double)px + the drawn offset;
+ * state, the stream after the five draws, where pbrt_gpu_li_device begins; inc;
+ * and, where not NULL, the pixel px, py. One kernel launch (k_frame_samples).
+ * Not served: the samples of n_dims >= 1, whose camera values are stratified,
+ * and EXACT mode, where a tile's samples share one stream. */
+typedef struct pbrt_frame_samples_soa {
+    double *ox, *oy, *oz, *dx, *dy, *dz;
+    double *tmax;                /* may be NULL                              */
+    double *pfilm_x, *pfilm_y;
+    uint64_t *state, *inc;
+    int32_t *px, *py;            /* may be NULL                              */
+} pbrt_frame_samples_soa;
+int pbrt_gpu_frame_samples_device(pbrt_gpu_ctx* ctx, const pbrt_frame_desc* desc,
+                                  const pbrt_frame_samples_soa* out);
+
+/* Adds the film of the samples of a tile range, in the frame layout with the
+ * caller's ns, to film_device: (H, W, 3) float64 XYZ over the cropped bounds,
+ * the buffer pbrt_gpu_render_async_into fills. PBRT_FILM_ADD_CLEAR zeroes the
+ * whole film first. Values and order are the reference's, as a frame's own
+ * kernels (k_film_cam, k_merge_film) compute them: a radiance with a NaN
+ * component becomes (0.1, 0.1, 0.1) (integrator.go:256-262); FilmTile.AddSample
+ * with sample weight 1 (film.go:211-248, its maxSampleLuminance test included);
+ * a tile-film pixel is the sum of the samples whose footprint holds it, source
+ * pixels in tile order and samples in order; RGBToXYZ per tile-film pixel
+ * (MergeFilmTile, film.go:115-132); the tiles of the range are added to a film
+ * pixel in ascending tile index, continuing from the value it holds. Ascending
+ * tile ranges over several calls (the first with the clear flag) therefore give
+ * the bits of one call over all tiles, which is how a caller bounds the memory
+ * of a frame. Two launches: k_film_add_tiles, k_film_add_merge.
+ *
+ * pfilm_x must lie in [px, px + 1) of its pixel, likewise pfilm_y; outside that
+ * range, or for a non-finite value, the sample's contribution is unspecified
+ * (other samples are unaffected: the kernel gathers, and no address is derived
+ * from a caller's value). PBRT_E_UNSUPPORTED besides the frame calls': a filter
+ * radius outside (0, tile_size), where a tile film would reach beyond its
+ * neighbouring tiles (pbrt_gpu_render refuses the same). */
+typedef struct pbrt_film_samples_soa {
+    const double *pfilm_x, *pfilm_y;
+    const double *r, *g, *b;
+} pbrt_film_samples_soa;
+int pbrt_gpu_film_add_device(pbrt_gpu_ctx* ctx, const pbrt_frame_desc* desc,
+                             const pbrt_film_samples_soa* samples, double* film_device);
+
+/* Film.WriteImage's pixel conversion (film.go:157-159) of a device film of w x h
+ * pixels to a device buffer of w * h * 4 bytes: pbrt_film_to_rgba8's bytes on
+ * every input (uint8(Clamp(v, 0, 1) * 255), a NaN as Go on amd64 converts it: 0;
+ * alpha 255). Any device film: a render's, a caller's, film_add's. One launch
+ * (k_film_rgba8), which stores a pixel's four bytes at once: rgba_device must
+ * be 4-byte aligned. PBRT_E_INVALID: a NULL or misaligned pointer, w or
+ * h <= 0, more than 2^31 - 1 pixels, a render in flight. */
+int pbrt_gpu_film_rgba8_device(pbrt_gpu_ctx* ctx, const double* film_device, int64_t w, int64_t h,
+                               uint8_t* rgba_device);
+
 /* Cancels the render in flight on ctx (from pbrt_gpu_render[_async[_into]]
  * entry until its pbrt_gpu_synchronize returns): the kernels poll a flag between
  * units of work (a pixel's chain, every 128 chain steps, a workgroup of paths),

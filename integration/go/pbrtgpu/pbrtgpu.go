@@ -557,6 +557,130 @@ func (r *Renderer) CameraRaysDevice(x0, y0, x1, y1 int64, filmOffset, lens [2]fl
 	return nil
 }
 
+// FrameRange is pbrt_frame_desc: the tiles [TileBegin, TileEnd) of the frame
+// layout (tiles in index order at TileSize, pixels row-major in their tile, Ns
+// consecutive samples per pixel; include/pbrt_gpu.h).
+type FrameRange struct {
+	TileSize, Ns       int32
+	TileBegin, TileEnd int64
+}
+
+func (f FrameRange) desc(flags int32) C.pbrt_frame_desc {
+	var d C.pbrt_frame_desc
+	d.tile_size, d.ns = C.int32_t(f.TileSize), C.int32_t(f.Ns)
+	d.tile_begin, d.tile_end = C.int64_t(f.TileBegin), C.int64_t(f.TileEnd)
+	d.flags, d.reserved = C.int32_t(flags), 0
+	return d
+}
+
+// FrameCount is the element count of a tile range (pbrt_gpu_frame_count): what
+// every array of FrameSamplesDevice and FilmAddDevice must hold.
+func (r *Renderer) FrameCount(f FrameRange) (int, error) {
+	d := f.desc(0)
+	n := int64(C.pbrt_gpu_frame_count(r.ctx, &d))
+	if n < 0 {
+		return 0, fmt.Errorf("pbrt_gpu_frame_count: tile range outside the film, or more than 2^31 - 1 samples")
+	}
+	return int(n), nil
+}
+
+// DeviceSamples are the outputs of FrameSamplesDevice: the rays (TMax may be
+// nil), PFilmX, PFilmY (float64: absolute raster positions), the stream after
+// the camera draws (DeviceRNG, where LiDevice begins) and, optionally, the
+// pixel (int32 each).
+type DeviceSamples struct {
+	Rays           DeviceRays
+	PFilmX, PFilmY *DeviceBuffer
+	RNG            DeviceRNG
+	Px, Py         *DeviceBuffer
+}
+
+// FrameSamplesDevice enqueues the traced samples (k = 1 .. Ns, spp = Ns + 1) of
+// a THROUGHPUT render with nDims = 0 over a tile range, in the frame layout
+// (pbrt_gpu_frame_samples_device). One kernel; nothing is copied or waited for.
+func (r *Renderer) FrameSamplesDevice(f FrameRange, out DeviceSamples) error {
+	n, err := r.FrameCount(f)
+	if err != nil {
+		return err
+	}
+	soa, err := r.raySoA(out.Rays, n)
+	if err != nil {
+		return err
+	}
+	p := [6]unsafe.Pointer{}
+	elem := [6]int{8, 8, 8, 8, 4, 4}
+	for k, d := range []*DeviceBuffer{out.PFilmX, out.PFilmY, out.RNG.State, out.RNG.Inc, out.Px, out.Py} {
+		if p[k], err = r.devPtr(d, n, elem[k], k > 3); err != nil {
+			return err
+		}
+	}
+	var s C.pbrt_frame_samples_soa
+	s.ox, s.oy, s.oz, s.dx, s.dy, s.dz, s.tmax = soa.ox, soa.oy, soa.oz, soa.dx, soa.dy, soa.dz, soa.tmax
+	s.pfilm_x, s.pfilm_y = (*C.double)(p[0]), (*C.double)(p[1])
+	s.state, s.inc = (*C.uint64_t)(p[2]), (*C.uint64_t)(p[3])
+	s.px, s.py = (*C.int32_t)(p[4]), (*C.int32_t)(p[5])
+	d := f.desc(0)
+	if rc := C.pbrt_gpu_frame_samples_device(r.ctx, &d, &s); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_frame_samples_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// FilmAddDevice adds the film of the samples of a tile range (PFilmX, PFilmY and
+// the radiances L.R, L.G, L.B, in the frame layout) to film, the (H, W, 3)
+// float64 XYZ film on the device; clear zeroes it first
+// (pbrt_gpu_film_add_device). Ascending ranges over several calls give the bits
+// of one call over all tiles. Two kernels; nothing is copied or waited for.
+func (r *Renderer) FilmAddDevice(f FrameRange, pFilmX, pFilmY *DeviceBuffer, L DeviceRadiance, film *DeviceBuffer, clear bool) error {
+	n, err := r.FrameCount(f)
+	if err != nil {
+		return err
+	}
+	p := [5]unsafe.Pointer{}
+	for k, d := range []*DeviceBuffer{pFilmX, pFilmY, L.R, L.G, L.B} {
+		if p[k], err = r.devPtr(d, n, 8, false); err != nil {
+			return err
+		}
+	}
+	fp, err := r.devPtr(film, r.w*r.h*3, 8, false)
+	if err != nil {
+		return err
+	}
+	var s C.pbrt_film_samples_soa
+	s.pfilm_x, s.pfilm_y = (*C.double)(p[0]), (*C.double)(p[1])
+	s.r, s.g, s.b = (*C.double)(p[2]), (*C.double)(p[3]), (*C.double)(p[4])
+	flags := int32(0)
+	if clear {
+		flags = C.PBRT_FILM_ADD_CLEAR
+	}
+	d := f.desc(flags)
+	if rc := C.pbrt_gpu_film_add_device(r.ctx, &d, &s, (*C.double)(fp)); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_film_add_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// FilmRGBA8Device converts a device film of w x h pixels to w * h * 4 bytes in
+// rgba, Film.WriteImage's conversion (pbrt_gpu_film_rgba8_device): the bytes of
+// FilmToRGBA's pixels on the host. One kernel; nothing is copied or waited for.
+func (r *Renderer) FilmRGBA8Device(film *DeviceBuffer, w, h int, rgba *DeviceBuffer) error {
+	if w <= 0 || h <= 0 || w > (1<<31-1)/h {
+		return fmt.Errorf("pbrtgpu: %d x %d pixels", w, h)
+	}
+	fp, err := r.devPtr(film, w*h*3, 8, false)
+	if err != nil {
+		return err
+	}
+	op, err := r.devPtr(rgba, w*h*4, 1, false)
+	if err != nil {
+		return err
+	}
+	if rc := C.pbrt_gpu_film_rgba8_device(r.ctx, (*C.double)(fp), C.int64_t(w), C.int64_t(h), (*C.uint8_t)(op)); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_film_rgba8_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
 // QueryPanics is pbrt_query_record: how many rays of the queries since the last
 // QueryStatus the reference panics on, the smallest such ray index (-1: none)
 // and its PBRT_PANIC_* kind.
