@@ -55,6 +55,10 @@ struct Knobs {
     bool cull_groups = true;   // PBRT_CULL_GROUPS=0
     bool film_add_lds = true;  // PBRT_FILM_ADD=direct: pbrt_gpu_film_add_device's tile films by the direct gather
                                // (k_film_add_tiles<false>) where the LDS-staged one would run
+    int direct_li_grid = 8192; // PBRT_DIRECT_LI_GRID=K: pbrt_gpu_direct_li_device's grid cap, 1 .. 65536 workgroups of
+                               // one wave, each striding over the work lists beyond; it bounds the kX kernels'
+                               // level records (direct_li_query.h). Measured on 2 M rays: 2048 is 7 % (Matte)
+                               // and 10 % (kX) slower, 16384 and more level
     static Knobs from_env() {
         Knobs k;
         auto ival = [](const char* n, int& out) { if (const char* e = getenv(n)) out = atoi(e); };
@@ -97,6 +101,7 @@ struct Knobs {
         ival("PBRT_CULL_GROUPS", cg);
         k.cull_groups = cg != 0;
         if (const char* e = getenv("PBRT_FILM_ADD")) k.film_add_lds = std::strcmp(e, "direct") != 0;
+        if (const char* e = getenv("PBRT_DIRECT_LI_GRID")) k.direct_li_grid = std::min(std::max(1, atoi(e)), 65536);
         return k;
     }
 };

@@ -46,7 +46,7 @@ inline int check_supported(const pbrt_li_desc& d, bool rough_glass, const char**
         *why = m;
         return (int)PBRT_E_UNSUPPORTED;
     };
-    if (d.integrator != PBRT_INTEGRATOR_PATH) return no("Path integrator only (DirectLighting Li is out of scope)");
+    if (d.integrator != PBRT_INTEGRATOR_PATH) return no("Path integrator only (DirectLighting.Li is pbrt_gpu_direct_li_device)");
     if (d.max_depth > kLiMaxDepth) return no("maxDepth > 2048");
     if (d.light_strategy != PBRT_LIGHT_STRATEGY_UNIFORM && d.light_strategy != PBRT_LIGHT_STRATEGY_POWER)
         return no("unsupported light sample strategy");

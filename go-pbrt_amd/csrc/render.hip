@@ -48,6 +48,7 @@
 #include "knobs.h"
 #include "mesh_bvh.h"
 #include "li_query.h"
+#include "direct_li_query.h"
 #include "film_query.h"
 #include "query_buffers.h"
 #include "render_kernels.h"
@@ -262,6 +263,9 @@ struct pbrt_gpu_ctx {
         pbrt_distribution_desc host_dist;
         int strategy = 0;   // the strategy d_dist holds (0: none yet)
     } li;
+    // pbrt_gpu_direct_li_device: the level records of k_li_direct<true, *>, [workgroup][level][field][lane]
+    // (grown on demand; sized by the capped grid and max_depth, direct_li_query.h)
+    DevBuf<double> d_dli_levels;
     // pbrt_gpu_film_add_device: the tile films of a call's tile range (grown on demand)
     DevBuf<double> d_fq_films;
     // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
@@ -630,6 +634,18 @@ const LiRow kLiKernels[] = {LI_ROW(false, 0), LI_ROW(true, 0), LI_ROW(false, 64)
 #undef LI_ROW
 LiKernel li_kernel(bool kx, int depth) {   // pbrt_gpu_li_device: kDepth 0 on an LDS-staged tree, 64 beyond
     for (const LiRow& r : kLiKernels)
+        if (r.kx == kx && r.depth == depth) return r.fn;
+    return nullptr;
+}
+
+using DirectLiKernel = decltype(&k_li_direct<false, 0>);
+struct DirectLiRow { bool kx; int depth; DirectLiKernel fn; const char* name; };
+#define DIRECT_LI_ROW(kx, depth) {kx, depth, &k_li_direct<kx, depth>, "k_li_direct<" #kx ", " #depth ">"}
+const DirectLiRow kDirectLiKernels[] = {DIRECT_LI_ROW(false, 0), DIRECT_LI_ROW(true, 0), DIRECT_LI_ROW(false, 64),
+                                        DIRECT_LI_ROW(true, 64)};
+#undef DIRECT_LI_ROW
+DirectLiKernel direct_li_kernel(bool kx, int depth) {   // pbrt_gpu_direct_li_device: chosen as li_kernel chooses
+    for (const DirectLiRow& r : kDirectLiKernels)
         if (r.kx == kx && r.depth == depth) return r.fn;
     return nullptr;
 }
@@ -1968,6 +1984,33 @@ int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_so
     return PBRT_OK;
 }
 
+// DirectLighting.Li over device arrays (k_li_direct.hip). The checks, the kernel choice, the capped grid and
+// the size of the level records: direct_li_query.h. No light distribution: one launch a call.
+int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* c, const pbrt_direct_li_desc* d, const pbrt_ray_soa* rays,
+                              const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out) {
+    const char* why = "";
+    if (int rc = pbrtdli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtdli::check_supported(*d, c->rough_glass, c->non_matte, &why)) return set_err(c, rc, why);
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = query_rec_ensure(c)) return rc;
+    const DevScene sc = with_slot(dev_scene(c, false), 7);
+    const pbrtdli::KernelArgs ka = pbrtdli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n,
+                                                        kLdsNodes, c->knobs.direct_li_grid, d->max_depth);
+    const DirectLiKernel kern = direct_li_kernel(ka.kx, ka.depth);
+    if (!kern) return set_err(c, PBRT_E_HIP, "no k_li_direct instantiation for depth " + std::to_string(ka.depth));
+    if (ka.level_doubles > 0)   // (grows only: a smaller query runs in the buffer of a larger one)
+        if (int rc = c->d_dli_levels.ensure(c, ka.level_doubles)) return rc;
+    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, (int)d->dl_strategy, ka.levels,
+             (int64_t)n, *rays, *rng, *out, c->d_qrec.get(), ka.level_doubles > 0 ? c->d_dli_levels.get() : nullptr);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+// (diagnostics) the capacity of the level-record buffer in bytes: it changes only when the buffer is allocated anew
+size_t pbrt_gpu_direct_li_scratch_bytes(const pbrt_gpu_ctx* c) { return c ? c->d_dli_levels.cap() * sizeof(double) : 0; }
+
 // ---- a frame from public pieces (k_film_q.hip). The layout, the checks and the refusals: film_query.h.
 // The RenderParams the film kernels' tile_bounds / film_tile_bounds read, for a tile size of the caller's.
 static RenderParams frame_params(const pbrt_gpu_ctx* c, const pbrtfilm::Layout& l) {
@@ -2370,7 +2413,7 @@ extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
 // kernel the library compiles, spelled as its explicit instantiation is
 // (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
-// k_paths_ci, k_paths_cam[_stack] and k_li families are named by their selectors' tables.
+// k_paths_ci, k_paths_cam[_stack], k_li and k_li_direct families are named by their selectors' tables.
 namespace {
 const KernelName kKernelNames[] = {
     // k_paths_m.hip, k_paths_x.hip
@@ -2442,6 +2485,7 @@ void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' ta
     for (const PathsCiRow& r : kPathsCiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const LiRow& r : kLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const DirectLiRow& r : kDirectLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const KernelName& k : kKernelNames) f(k.fn, k.name);
     size_t nm = 0;
     const KernelName* mk = mesh_bvh_kernel_names(&nm);
@@ -2477,6 +2521,8 @@ extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a,
         fn = reinterpret_cast<const void*>(serial_kernel(a[0]));
     else if (f == "k_li" && n == 2)
         fn = reinterpret_cast<const void*>(li_kernel(a[0] != 0, a[1]));
+    else if (f == "k_li_direct" && n == 2)
+        fn = reinterpret_cast<const void*>(direct_li_kernel(a[0] != 0, a[1]));
     return fn ? kernel_name_of(fn, nullptr) : nullptr;
 }
 

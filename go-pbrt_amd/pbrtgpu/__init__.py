@@ -68,6 +68,8 @@ def lib():
     abi.declare_query(L)
     if hasattr(L, "pbrt_gpu_li_device"):   # (a library of an earlier build, PBRT_GPU_LIB, has no such entry)
         abi.declare_li(L)
+    if hasattr(L, "pbrt_gpu_direct_li_device"):
+        abi.declare_direct_li(L)
     if hasattr(L, "pbrt_gpu_film_add_device"):
         abi.declare_frame(L)
     abi.declare_launch_log(L)
@@ -572,6 +574,22 @@ def _soa(struct, bufs):
     return s
 
 
+def _li_soas(renderer, what, rays, rng, n, out):
+    """The checked (RaySoA, RngSoA, RadianceSoA) of a Li query (li_device, direct_li_device):
+    rng a dict or a (state, inc) pair; out holds r, g, b and any of state, draws, rays."""
+    if not isinstance(rng, dict):
+        rng = dict(zip(RNG_KEYS, tuple(rng)))
+    unknown = (set(out) - set(LI_DTYPES)) | (set(rng) - set(RNG_KEYS))
+    missing = [k for k in ("r", "g", "b") if out.get(k) is None] + [k for k in RNG_KEYS if rng.get(k) is None]
+    if unknown or missing:
+        raise PbrtError(abi.PBRT_E_INVALID, f"{what}: unknown {sorted(unknown)}, missing {missing}")
+    rb = _ray_bufs(rays)
+    gb = [(k, rng[k], np.uint64) for k in RNG_KEYS]
+    ob = [(k, out[k], dt) for k, dt in LI_DTYPES.items() if out.get(k) is not None]
+    check_buffers(renderer, n, rb + gb + ob)
+    return _soa(abi.RaySoA, rb), _soa(abi.RngSoA, gb), _soa(abi.RadianceSoA, ob)
+
+
 # --------------------------------------------------------------------- renderer
 class Renderer:
     """pbrt_gpu_ctx: the scene resident on one GPU."""
@@ -813,19 +831,24 @@ class Renderer:
         its PCG32 draws) and rays (uint32: closest | shadow << 16). Enqueue only, like
         intersect_device; a ray on which the reference panics has L = 0 and is counted in
         query_status(). Returns the status (PBRT_E_UNSUPPORTED: last_error() says why)."""
-        if not isinstance(rng, dict):
-            rng = dict(zip(RNG_KEYS, tuple(rng)))
-        unknown = (set(out) - set(LI_DTYPES)) | (set(rng) - set(RNG_KEYS))
-        missing = [k for k in ("r", "g", "b") if out.get(k) is None] + [k for k in RNG_KEYS if rng.get(k) is None]
-        if unknown or missing:
-            raise PbrtError(abi.PBRT_E_INVALID, f"li_device: unknown {sorted(unknown)}, missing {missing}")
-        rb = _ray_bufs(rays)
-        gb = [(k, rng[k], np.uint64) for k in RNG_KEYS]
-        ob = [(k, out[k], dt) for k, dt in LI_DTYPES.items() if out.get(k) is not None]
-        check_buffers(self, n, rb + gb + ob)
+        rs, gs, os_ = _li_soas(self, "li_device", rays, rng, n, out)
         d = abi.li_desc(max_depth, light_strategy, rr_threshold, integrator)
-        rs, gs, os_ = _soa(abi.RaySoA, rb), _soa(abi.RngSoA, gb), _soa(abi.RadianceSoA, ob)
         return lib().pbrt_gpu_li_device(self.h, C.byref(d), C.byref(rs), C.byref(gs), n, C.byref(os_))
+
+    def direct_li_device(self, rays, rng, n, out, max_depth=5, dl_strategy=abi.PBRT_DL_UNIFORM_SAMPLE_ALL):
+        """pbrt_gpu_direct_li_device: DirectLighting.Li of rays[0:n], with li_device's buffers,
+        outputs and buffer checks: ray i on the PCG32 stream (rng["state"][i], rng["inc"][i]), into
+        r, g, b (required) and any of state, draws and rays (closest | shadow << 16). Enqueue
+        only; a ray on which the reference panics has L = 0 and is counted in query_status().
+        Returns the status (PBRT_E_UNSUPPORTED: last_error() says why)."""
+        rs, gs, os_ = _li_soas(self, "direct_li_device", rays, rng, n, out)
+        d = abi.direct_li_desc(max_depth, dl_strategy)
+        return lib().pbrt_gpu_direct_li_device(self.h, C.byref(d), C.byref(rs), C.byref(gs), n, C.byref(os_))
+
+    def direct_li_scratch_bytes(self):
+        """pbrt_gpu_direct_li_scratch_bytes: the size of direct_li_device's level-record buffer (it
+        changes only when a call allocates; 0 on a Matte-only scene)."""
+        return lib().pbrt_gpu_direct_li_scratch_bytes(self.h)
 
     def last_error(self):
         """pbrt_gpu_last_error: the reason of the context's last refusal."""
@@ -924,17 +947,23 @@ class Renderer:
         return [(b, min(b + per, nt), self.frame_count(ns, b, min(b + per, nt), tile_size)) for b in range(0, nt, per)]
 
     def render_samples(self, spp, max_depth=10, light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0,
-                       tile_size=16, budget_bytes=1 << 30, film=None, count_rays=False):
+                       tile_size=16, budget_bytes=1 << 30, film=None, count_rays=False,
+                       integrator=abi.PBRT_INTEGRATOR_PATH, dl_strategy=abi.PBRT_DL_UNIFORM_SAMPLE_ALL):
         """A THROUGHPUT frame with n_dims = 0 composed of the public stages: per ascending tile
         range sized to budget_bytes, frame_samples, li_device and film_add, all on the device; the
         film is pbrt_gpu_render's, bit for bit. film: a float64 DeviceBuffer of H * W * 3 to
-        compose into (None: one of the call's own). Returns (the (H, W, 3) film, info): info has
-        the ranges, the samples and, with count_rays, the reference's closest and shadow ray
-        counts (which downloads 4 bytes per sample). Raises PbrtError on a refusal and
+        compose into (None: one of the call's own). integrator: PBRT_INTEGRATOR_PATH, or
+        PBRT_INTEGRATOR_DIRECT_LIGHTING, whose Li stage is direct_li_device with dl_strategy
+        (light_strategy and rr_threshold are Path's alone). Returns (the (H, W, 3) film, info):
+        info has the ranges, the samples and, with count_rays, the reference's closest and shadow
+        ray counts (which downloads 4 bytes per sample). Raises PbrtError on a refusal and
         PBRT_E_REF_PANIC when the reference panics on a path."""
         ns = int(spp) - 1
         if ns < 1:
             raise PbrtError(abi.PBRT_E_INVALID, "render_samples: spp >= 2 (sample 0 of a pixel is never traced)")
+        if integrator not in (abi.PBRT_INTEGRATOR_PATH, abi.PBRT_INTEGRATOR_DIRECT_LIGHTING):
+            raise PbrtError(abi.PBRT_E_INVALID, f"render_samples: integrator {integrator}")
+        direct = integrator == abi.PBRT_INTEGRATOR_DIRECT_LIGHTING
         ranges = self.frame_ranges(ns, tile_size, budget_bytes)
         cap = max(n for _, _, n in ranges)
         own = []
@@ -953,7 +982,10 @@ class Renderer:
             closest = shadow = 0
             for i, (b, e, n) in enumerate(ranges):
                 self._check(self.frame_samples(sb, ns, b, e, tile_size))
-                self._check(self.li_device(rays, rng, n, ob, max_depth, light_strategy, rr_threshold))
+                if direct:
+                    self._check(self.direct_li_device(rays, rng, n, ob, max_depth, dl_strategy))
+                else:
+                    self._check(self.li_device(rays, rng, n, ob, max_depth, light_strategy, rr_threshold))
                 self._check(self.film_add(fs, ns, film, b, e, tile_size, clear=i == 0))
                 if count_rays:
                     v = ob["rays"].download()[:n]
@@ -977,10 +1009,18 @@ class Renderer:
         desc is li_device's (max_depth, light_strategy, rr_threshold). Returns (L (n, 3),
         state, draws, rays); raises PbrtError on a refusal and PBRT_E_REF_PANIC when the
         reference panics on a ray (its stats field is the QueryRecord)."""
+        return self._host_radiance("radiance", self.li_device, rays, state, inc, desc)
+
+    def direct_radiance(self, rays, state, inc, **desc):
+        """DirectLighting.Li of host rays, in the shape of radiance: desc is direct_li_device's
+        (max_depth, dl_strategy). Returns (L (n, 3), state, draws, rays)."""
+        return self._host_radiance("direct_radiance", self.direct_li_device, rays, state, inc, desc)
+
+    def _host_radiance(self, what, query, rays, state, inc, desc):
         rays = np.ascontiguousarray(rays, dtype=np.float64)
         n = rays.shape[0]
         if rays.ndim != 2 or rays.shape[1] not in (6, 7) or len(state) != n or len(inc) != n:
-            raise PbrtError(abi.PBRT_E_INVALID, "radiance: rays (n, 6) or (n, 7), state and inc of n elements")
+            raise PbrtError(abi.PBRT_E_INVALID, f"{what}: rays (n, 6) or (n, 7), state and inc of n elements")
         if n == 0:
             return np.zeros((0, 3)), np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32)
         bufs = []
@@ -989,7 +1029,7 @@ class Renderer:
             gb = [self.upload(np.asarray(a, dtype=np.uint64)) for a in (state, inc)]
             ob = {k: self.buffer(n, dt) for k, dt in LI_DTYPES.items()}
             bufs = rb + gb + list(ob.values())
-            self._check(self.li_device(tuple(rb), tuple(gb), n, ob, **desc))
+            self._check(query(tuple(rb), tuple(gb), n, ob, **desc))
             rc, rec = self.query_status()
             if rc:
                 raise PbrtError(rc, self.last_error(), rec)

@@ -425,6 +425,27 @@ def declare_li(L):
     L.pbrt_gpu_li_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]
 
 
+class DirectLiDesc(C.Structure):
+    """pbrt_direct_li_desc: what pbrt_gpu_direct_li_device needs of a DirectLighting render desc."""
+    _fields_ = [("max_depth", C.c_int32), ("dl_strategy", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+DIRECT_LI_SYMBOLS = ("pbrt_gpu_direct_li_device", "pbrt_gpu_direct_li_scratch_bytes")
+
+
+def direct_li_desc(max_depth=5, dl_strategy=PBRT_DL_UNIFORM_SAMPLE_ALL, reserved=(0, 0)):
+    """DirectLiDesc with render_desc's strategy and the DirectLighting integrator's default depth."""
+    return DirectLiDesc(max_depth, dl_strategy, (C.c_int32 * 2)(*reserved))
+
+
+def declare_direct_li(L):
+    """ctypes prototypes of pbrt_gpu_direct_li_device and its diagnostic (apart, like declare_li)."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_direct_li_device.argtypes = [vp, P(DirectLiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]
+    L.pbrt_gpu_direct_li_scratch_bytes.argtypes = [vp]
+    L.pbrt_gpu_direct_li_scratch_bytes.restype = C.c_size_t
+
+
 # --------------------------------- a frame from public pieces (include/pbrt_gpu.h)
 PBRT_FILM_ADD_CLEAR = 1
 

@@ -147,6 +147,8 @@ int pbrt_gpu_kernel_names(const char** out, int n);
  *   "k_paths_ci"     3: P, mb, kx
  *   "k_paths_cam"    3: P, mb, stack (1: k_paths_cam_stack)
  *   "k_render_exact" 1: min_waves
+ *   "k_li"           2: kx, depth (0, 64)
+ *   "k_li_direct"    2: kx, depth (0, 64)
  * NULL for any other family or argument count. */
 const char* pbrt_diag_kernel_choice(const char* family, const int* args, int n);
 /* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */
@@ -157,6 +159,13 @@ int64_t pbrt_gpu_lds_per_block(struct pbrt_gpu_ctx* ctx);
  * call's size, so a value that stays the same across calls shows that they
  * allocated nothing. 0 before the first film_add. */
 size_t pbrt_gpu_film_scratch_bytes(const struct pbrt_gpu_ctx* ctx);
+/* Bytes of the buffer in which pbrt_gpu_direct_li_device's kX kernels keep the
+ * level records of the recursion through smooth glass: the call's one
+ * allocation, grid * levels(max_depth) * 64 lanes * 56 B with the grid capped
+ * (PBRT_DIRECT_LI_GRID), so independent of n beyond the cap. Allocated anew only
+ * when a call needs more than it holds; 0 before the first such call, and for
+ * ever on a Matte-only scene. */
+size_t pbrt_gpu_direct_li_scratch_bytes(const struct pbrt_gpu_ctx* ctx);
 
 /* pbrt_gpu_intersect_device / pbrt_gpu_intersect_p_device (pbrt_gpu.h: the same
  * buffers, record and status) through the LDS-staged walks of the render

@@ -501,6 +501,57 @@ typedef struct pbrt_radiance_soa {
 int pbrt_gpu_li_device(pbrt_gpu_ctx* ctx, const pbrt_li_desc* desc, const pbrt_ray_soa* rays,
                        const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out);
 
+/* The Integrator interface's other implementation over the same arrays: ray i
+ * of the batch gets DirectLighting.Li(ray_i, scene, sampler, depth 0)
+ * (directlighting.go:62-104, integrator.go:23-77, 352-422), where the sampler is
+ * sampler.RandomSampler on the PCG32 stream (rng->state[i], rng->inc[i]): every
+ * Get1D / Get2D is a draw of that stream, in the reference's order, and no
+ * dimension is stratified. Per level: UniformSampleAllLights (4 draws a light)
+ * or UniformSampleOneLight without a distribution (5 draws, and its "> 10"
+ * panic), then, where depth + 1 < max_depth, the Get2D of SpecularReflect
+ * (black for every supported material) and of SpecularTransmit, which recurses
+ * at depth + 2 through smooth glass with the local-frame wi (SURVEY #7, #23).
+ * One kernel (k_li_direct) runs the batch with the arithmetic of the render
+ * kernels, so a value is the bits a DirectLighting frame would add to its film
+ * for the same ray and stream. The ray's time is 0; rays->tmax may be NULL
+ * (+Inf).
+ *
+ * The outputs are pbrt_gpu_li_device's: out->r/g/b receive Li's return value;
+ * the optional state, draws and rays (closest-hit queries in the low 16 bits,
+ * visibility rays in the high 16) may each be NULL. Li does not replace a NaN
+ * radiance. A ray on which the reference panics (PBRT_PANIC_LD_GT_10 of
+ * UniformSampleOneLight included) has r = g = b = 0, its optional outputs hold
+ * the values at the panic, and it is counted in the context's query record
+ * (pbrt_gpu_query_status).
+ *
+ * Ordering and memory are pbrt_gpu_intersect_device's: every pointer is a device
+ * pointer to n elements; the call only enqueues on the context's stream, after
+ * everything already on it; n == 0 is PBRT_OK and launches nothing.
+ * DirectLighting has no light distribution: nothing is uploaded and every call
+ * is one kernel launch. On a scene with Mirror / Glass / OrenNayar materials the
+ * kernel keeps the recursion's level records (56 B a level and lane) in a buffer
+ * the context owns, sized by the launch's capped grid and max_depth and never by
+ * n; it grows on demand (a second call at the same or a smaller size allocates
+ * nothing; pbrt_gpu_direct_li_scratch_bytes, pbrt_diag.h) and is freed with the
+ * context. A Matte-only scene has no such buffer.
+ *
+ * PBRT_E_INVALID, before any device call: a NULL context, desc, rays, ray
+ * pointer other than tmax, rng, rng->state, rng->inc, out, out->r/g/b;
+ * n > 2^31 - 1; max_depth < 1; a reserved field != 0; or a render in flight
+ * (left untouched). PBRT_E_UNSUPPORTED, with the reason in pbrt_gpu_last_error:
+ * an unknown dl_strategy; a scene with rough glass; max_depth > 64 on a scene
+ * with Mirror / Glass / OrenNayar materials (a DirectLighting render's own rule:
+ * the level records hold 32 levels). On a Matte-only scene the recursion cannot
+ * start and any max_depth >= 1 is served. The rays that only PBRT_FLAG_PANIC_FIDELITY
+ * traces are not traced, as in pbrt_gpu_li_device. */
+typedef struct pbrt_direct_li_desc {
+    int32_t max_depth;    /* >= 1                                               */
+    int32_t dl_strategy;  /* PBRT_DL_UNIFORM_SAMPLE_ALL | PBRT_DL_UNIFORM_SAMPLE_ONE */
+    int32_t reserved[2];  /* 0                                                  */
+} pbrt_direct_li_desc;
+int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* ctx, const pbrt_direct_li_desc* desc, const pbrt_ray_soa* rays,
+                              const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out);
+
 /* ---------------------------------------------- a frame from public pieces
  * Three enqueue-only calls that, with pbrt_gpu_li_device between the first two,
  * build a frame on the device: samples, Li, film, RGBA8. The composed film is a

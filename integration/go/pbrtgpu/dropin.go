@@ -384,14 +384,24 @@ func (p *Path) RenderFrame(ctx context.Context, scene pbrt.Scene, tileSize int64
 // keeps the integrator's maxDepth, rrThreshold and strategy. The arrays cross the
 // boundary in one C.malloc'd arena; the device buffers live for the call.
 func (p *Path) LiBatch(rays []*pbrt.Ray, state, inc []uint64, L [][3]float64) (QueryPanics, error) {
+	r, ok := p.renderer.(*Renderer)
+	if !ok || r == nil {
+		return QueryPanics{}, errors.New("pbrtgpu: LiBatch needs a Path rendering on one device (call RenderFrame first)")
+	}
+	return liBatch(r, rays, state, inc, L, func(dr DeviceRays, rng DeviceRNG, n int, out DeviceRadiance) error {
+		return r.LiDevice(dr, rng, n, int32(p.rd.max_depth), float64(p.rd.rr_threshold), int32(p.rd.light_strategy), out)
+	})
+}
+
+// liBatch is the host side of a LiBatch: the rays and streams up, one Li query
+// (Renderer.LiDevice or Renderer.DirectLiDevice), the query record, the radiances
+// down.
+func liBatch(r *Renderer, rays []*pbrt.Ray, state, inc []uint64, L [][3]float64,
+	query func(DeviceRays, DeviceRNG, int, DeviceRadiance) error) (QueryPanics, error) {
 	var none QueryPanics
 	n := len(rays)
 	if len(state) < n || len(inc) < n || len(L) < n {
 		return none, fmt.Errorf("pbrtgpu: %d rays need as many states, increments and results", n)
-	}
-	r, ok := p.renderer.(*Renderer)
-	if !ok || r == nil {
-		return none, errors.New("pbrtgpu: LiBatch needs a Path rendering on one device (call RenderFrame first)")
 	}
 	if n == 0 {
 		return none, nil
@@ -435,8 +445,7 @@ func (p *Path) LiBatch(rays []*pbrt.Ray, state, inc []uint64, L [][3]float64) (Q
 	}
 	dr := DeviceRays{bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], bufs[5], bufs[6]}
 	out := DeviceRadiance{R: bufs[9], G: bufs[10], B: bufs[11]}
-	if err := r.LiDevice(dr, DeviceRNG{bufs[7], bufs[8]}, n, int32(p.rd.max_depth), float64(p.rd.rr_threshold),
-		int32(p.rd.light_strategy), out); err != nil {
+	if err := query(dr, DeviceRNG{bufs[7], bufs[8]}, n, out); err != nil {
 		return none, err
 	}
 	qp, err := r.QueryStatus()
@@ -458,6 +467,78 @@ func (p *Path) LiBatch(rays []*pbrt.Ray, state, inc []uint64, L [][3]float64) (Q
 func (p *Path) Close() {
 	if p.renderer != nil {
 		p.renderer.Close()
+	}
+}
+
+// DirectLighting is integrator.NewDirectLighting (directlighting.go:27-37) with a
+// GPU RenderFrame and LiBatch, on one device.
+type DirectLighting struct {
+	pbrt.Integrator // the CPU integrator.DirectLighting: Li, Preprocess, GetSampler, GetCamera, Specular*
+
+	rec    *Recorder
+	rd     C.pbrt_render_desc
+	device int
+
+	once     sync.Once
+	renderer *Renderer
+	err      error
+}
+
+// NewDirectLighting is integrator.NewDirectLighting(strategy, maxDepth, camera,
+// sampler, pixelBounds); device is the HIP ordinal the frame renders on.
+func (r *Recorder) NewDirectLighting(strategy integrator.LightStrategy, maxDepth int, camera pbrt.Camera, smp *Stratified,
+	pixelBounds *pbrt.Bounds2i, device int) *DirectLighting {
+	rd := DirectLightingDesc(smp.X, smp.Y, smp.Jitter, int32(smp.NDims), int32(maxDepth), int32(strategy))
+	return &DirectLighting{
+		Integrator: integrator.NewDirectLighting(strategy, maxDepth, camera, smp, pixelBounds),
+		rec:        r,
+		rd:         rd,
+		device:     device,
+	}
+}
+
+// RenderFrame implements pbrt.FrameRenderer as Path.RenderFrame does, for the
+// DirectLighting integrator.
+func (d *DirectLighting) RenderFrame(ctx context.Context, scene pbrt.Scene, tileSize int64) error {
+	if err := d.rec.build(); err != nil {
+		return pbrt.RenderTiles(ctx, d, scene, tileSize)
+	}
+	d.once.Do(func() { d.renderer, d.err = NewRenderer(d.rec.sb, d.device) })
+	if d.err != nil {
+		return d.err
+	}
+	film := d.GetCamera().GetFilm()
+	b := film.CroppedPixelBounds
+	xyz := make([]float64, (b.Max.X-b.Min.X)*(b.Max.Y-b.Min.Y)*3)
+	rd := d.rd
+	rd.tile_size = C.int64_t(tileSize)
+	if err := d.renderer.RenderFrame(ctx, &rd, xyz); err != nil {
+		return err
+	}
+	film.MergeXYZ(xyz)
+	film.WriteImage(1.0)
+	return nil
+}
+
+// LiBatch is DirectLighting.Li (directlighting.go:62-104) for a batch of the
+// caller's own rays on the GPU (Renderer.DirectLiDevice), in the shape of
+// Path.LiBatch: ray i samples with a sampler.RandomSampler on the PCG32 stream
+// (state[i], inc[i]), depth 0, with the integrator's maxDepth and strategy. It
+// needs a frame rendered first (RenderFrame creates the device scene).
+func (d *DirectLighting) LiBatch(rays []*pbrt.Ray, state, inc []uint64, L [][3]float64) (QueryPanics, error) {
+	r := d.renderer
+	if r == nil {
+		return QueryPanics{}, errors.New("pbrtgpu: LiBatch needs a rendered frame (call RenderFrame first)")
+	}
+	return liBatch(r, rays, state, inc, L, func(dr DeviceRays, rng DeviceRNG, n int, out DeviceRadiance) error {
+		return r.DirectLiDevice(dr, rng, n, int32(d.rd.max_depth), int32(d.rd.dl_strategy), out)
+	})
+}
+
+// Close releases the device scene.
+func (d *DirectLighting) Close() {
+	if d.renderer != nil {
+		d.renderer.Close()
 	}
 }
 

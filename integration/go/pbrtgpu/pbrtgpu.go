@@ -191,6 +191,16 @@ func PathDesc(xs, ys int32, jitter bool, nDims, maxDepth int32, rrThreshold floa
 	return rd
 }
 
+// DirectLightingDesc is integrator.NewDirectLighting(strategy, maxDepth, camera,
+// sampler, ...) with sampler.NewStratified(xs, ys, jitter, nDims); strategy is
+// integrator.UniformSampleAll (1) or UniformSampleOne (2), PBRT_DL_*'s values.
+func DirectLightingDesc(xs, ys int32, jitter bool, nDims, maxDepth, strategy int32) C.pbrt_render_desc {
+	rd := PathDesc(xs, ys, jitter, nDims, maxDepth, 1, C.PBRT_LIGHT_STRATEGY_UNIFORM)
+	rd.integrator = C.PBRT_INTEGRATOR_DIRECT_LIGHTING
+	rd.dl_strategy = C.int32_t(strategy)
+	return rd
+}
+
 // WithRandomSampler switches rd to sampler.NewRandomSampler(ns, seed) (random.go:12-57).
 func WithRandomSampler(rd *C.pbrt_render_desc, ns int32) { C.pbrt_random_sampler(C.int32_t(ns), rd) }
 
@@ -530,6 +540,40 @@ func (r *Renderer) LiDevice(rays DeviceRays, rng DeviceRNG, n int, maxDepth int3
 	ld.rr_threshold = C.double(rrThreshold)
 	if rc := C.pbrt_gpu_li_device(r.ctx, &ld, &soa, &gs, C.size_t(n), &rs); rc != C.PBRT_OK {
 		return fmt.Errorf("pbrt_gpu_li_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// DirectLiDevice enqueues DirectLighting.Li(ray, scene, sampler, 0) for rays[0:n]
+// on the context's stream (pbrt_gpu_direct_li_device), with LiDevice's buffers and
+// outputs: ray i samples with a RandomSampler on the stream (State[i], Inc[i]).
+// strategy is PBRT_DL_UNIFORM_SAMPLE_ALL (1) or PBRT_DL_UNIFORM_SAMPLE_ONE (2).
+// A ray on which the reference panics (UniformSampleOneLight's "> 10" included)
+// has L = 0 and is counted in QueryStatus' record. An unknown strategy, rough
+// glass and maxDepth > 64 on a scene with Mirror / Glass / OrenNayar materials are
+// refused with the reason.
+func (r *Renderer) DirectLiDevice(rays DeviceRays, rng DeviceRNG, n int, maxDepth int32, strategy int32,
+	out DeviceRadiance) error {
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return err
+	}
+	var gs C.pbrt_rng_soa
+	var rs C.pbrt_radiance_soa
+	p := [8]unsafe.Pointer{}
+	elem := [8]int{8, 8, 8, 8, 8, 8, 4, 4}
+	for k, d := range []*DeviceBuffer{rng.State, rng.Inc, out.R, out.G, out.B, out.State, out.Draws, out.Rays} {
+		if p[k], err = r.devPtr(d, n, elem[k], k > 4); err != nil {
+			return err
+		}
+	}
+	gs.state, gs.inc = (*C.uint64_t)(p[0]), (*C.uint64_t)(p[1])
+	rs.r, rs.g, rs.b = (*C.double)(p[2]), (*C.double)(p[3]), (*C.double)(p[4])
+	rs.state, rs.draws, rs.rays = (*C.uint64_t)(p[5]), (*C.uint32_t)(p[6]), (*C.uint32_t)(p[7])
+	var dd C.pbrt_direct_li_desc // (reserved stays zero)
+	dd.max_depth, dd.dl_strategy = C.int32_t(maxDepth), C.int32_t(strategy)
+	if rc := C.pbrt_gpu_direct_li_device(r.ctx, &dd, &soa, &gs, C.size_t(n), &rs); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_direct_li_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
 	}
 	return nil
 }
