@@ -199,6 +199,13 @@ __device__ __forceinline__ void add_L(PathState& s, Spec v) { s.L = s.L + v; }
 __device__ __forceinline__ void add_L(PathStateLds& s, Spec v) { *s.L = *s.L + v; }
 __device__ __forceinline__ void add_rays(PathState& s, uint32_t v) { s.rays += v; }
 __device__ __forceinline__ void add_rays(PathStateLds& s, uint32_t v) { *s.rays += v; }
+// path_step's hooks are overloads on its State, found at instantiation: add_L,
+// add_rays, and note_hit, called once an iteration's closest-hit traversal has
+// found a hit without a panic (s.ray.tmax is then the hit's distance). The two
+// states above take no note, and no code is generated for them; a state of
+// another unit that surfaces the interaction has its own (k_path_step.hip).
+__device__ __forceinline__ void note_hit(PathState&, const DevScene&, const SI&) {}
+__device__ __forceinline__ void note_hit(PathStateLds&, const DevScene&, const SI&) {}
 // kWhich: 0 any iteration, 1 only the first (s.first == 1: bounce 1 from the
 // pixel cache, no traversal), 2 only later ones (s.first == 0).
 //
@@ -238,6 +245,7 @@ __device__ __forceinline__ bool path_step(const DevScene& sc, const Cache& pc, c
         const bool hit = bvh_traverse<false, PBRT_PATHS_LB>(sc, s.ray, &isect, stack, panic);
         if (!hit) return true;
         if (panic) return true;
+        note_hit(s, sc, isect);
         if ((kX ? compute_bsdf_x(sc, isect, b, x) : compute_bsdf(sc, isect, b)) < 0) {
             panic = -1;
             return true;

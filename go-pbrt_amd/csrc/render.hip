@@ -49,6 +49,7 @@
 #include "mesh_bvh.h"
 #include "li_query.h"
 #include "direct_li_query.h"
+#include "path_query.h"
 #include "film_query.h"
 #include "query_buffers.h"
 #include "render_kernels.h"
@@ -646,6 +647,18 @@ const DirectLiRow kDirectLiKernels[] = {DIRECT_LI_ROW(false, 0), DIRECT_LI_ROW(t
 #undef DIRECT_LI_ROW
 DirectLiKernel direct_li_kernel(bool kx, int depth) {   // pbrt_gpu_direct_li_device: chosen as li_kernel chooses
     for (const DirectLiRow& r : kDirectLiKernels)
+        if (r.kx == kx && r.depth == depth) return r.fn;
+    return nullptr;
+}
+
+using PathStepKernel = decltype(&k_path_step<false, 0>);
+struct PathStepRow { bool kx; int depth; PathStepKernel fn; const char* name; };
+#define PATH_STEP_ROW(kx, depth) {kx, depth, &k_path_step<kx, depth>, "k_path_step<" #kx ", " #depth ">"}
+const PathStepRow kPathStepKernels[] = {PATH_STEP_ROW(false, 0), PATH_STEP_ROW(true, 0), PATH_STEP_ROW(false, 64),
+                                        PATH_STEP_ROW(true, 64)};
+#undef PATH_STEP_ROW
+PathStepKernel path_step_kernel(bool kx, int depth) {   // pbrt_gpu_path_step_device: chosen as li_kernel chooses
+    for (const PathStepRow& r : kPathStepKernels)
         if (r.kx == kx && r.depth == depth) return r.fn;
     return nullptr;
 }
@@ -1947,6 +1960,27 @@ int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d,
     return PBRT_OK;
 }
 
+// The light distribution of a Li query's strategy in the query's own buffer (li_device, path_step_device):
+// built, checked and uploaded when the strategy differs from the one last uploaded. n == 0 uploads nothing.
+static int li_distribution(pbrt_gpu_ctx* c, const pbrt_li_desc* d, size_t n) {
+    const char* why = "";
+    if (c->li.strategy == d->light_strategy) return PBRT_OK;
+    // (a refused strategy leaves the uploaded one in place)
+    pbrt_distribution_desc dist;
+    if (int rc = pbrt_scene_light_distribution(&c->host_scene, d->light_strategy, &dist))
+        return set_err(c, rc, "unsupported light sample strategy");
+    if (int rc = pbrtli::check_distribution(c->host_scene.n_lights, dist.func, dist.count, dist.func_int, &why))
+        return set_err(c, rc, why);
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = c->li.d_dist.ensure(c, 1)) return rc;
+    c->li.host_dist = dist;
+    c->li.strategy = 0;
+    HIPCHK(c, hipMemcpyAsync(c->li.d_dist.get(), &c->li.host_dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
+    c->li.strategy = d->light_strategy;
+    return PBRT_OK;
+}
+
 // Integrator.Li over device arrays (k_li.hip). The checks and the kernel choice: li_query.h.
 int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng,
                        size_t n, const pbrt_radiance_soa* out) {
@@ -1954,21 +1988,7 @@ int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_so
     if (int rc = pbrtli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
         return set_err(c, rc, why);
     if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
-    const bool new_dist = c->li.strategy != d->light_strategy;
-    if (new_dist) {   // (a refused strategy leaves the uploaded one in place)
-        pbrt_distribution_desc dist;
-        if (int rc = pbrt_scene_light_distribution(&c->host_scene, d->light_strategy, &dist))
-            return set_err(c, rc, "unsupported light sample strategy");
-        if (int rc = pbrtli::check_distribution(c->host_scene.n_lights, dist.func, dist.count, dist.func_int, &why))
-            return set_err(c, rc, why);
-        if (n == 0) return PBRT_OK;
-        HIPCHK(c, hipSetDevice(c->device));
-        if (int rc = c->li.d_dist.ensure(c, 1)) return rc;
-        c->li.host_dist = dist;
-        c->li.strategy = 0;
-        HIPCHK(c, hipMemcpyAsync(c->li.d_dist.get(), &c->li.host_dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
-        c->li.strategy = d->light_strategy;
-    }
+    if (int rc = li_distribution(c, d, n)) return rc;
     if (n == 0) return PBRT_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (int rc = query_rec_ensure(c)) return rc;
@@ -1980,6 +2000,45 @@ int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_so
     if (!kern) return set_err(c, PBRT_E_HIP, "no k_li instantiation for depth " + std::to_string(ka.depth));
     launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
              *rays, *rng, *out, c->d_qrec.get());
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+// Path.Li one iteration at a time over device path state (k_path_step.hip). The checks, the queue rules and the
+// grids: path_query.h; the desc's refusals, the distribution and the instantiation's choice are the li query's.
+int pbrt_gpu_path_begin_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng, size_t n,
+                               const pbrt_path_soa* paths) {
+    const char* why = "";
+    if (int rc = pbrtpath::check_begin(c != nullptr, rays, rng, n, paths, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    launch_k(c, k_path_begin, dim3(pbrtpath::begin_grid(n)), dim3(pbrtpath::kBeginBlock), 0, c->stream, (int64_t)n, *rays,
+             *rng, *paths);
+    HIPCHK(c, hipGetLastError());
+    return PBRT_OK;
+}
+
+int pbrt_gpu_path_step_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_path_soa* paths, const pbrt_path_queue* in,
+                              const pbrt_path_queue* out, size_t n, const pbrt_path_step_soa* step) {
+    const char* why = "";
+    if (int rc = pbrtpath::check_step(c != nullptr, d, paths, in, out, n, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
+    if (int rc = li_distribution(c, d, n)) return rc;
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = query_rec_ensure(c)) return rc;
+    DevScene sc = with_slot(dev_scene(c, false), 7);
+    sc.dist = c->li.d_dist.get();
+    const pbrtli::KernelArgs ka =
+        pbrtpath::step_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
+    const PathStepKernel kern = path_step_kernel(ka.kx, ka.depth);
+    if (!kern) return set_err(c, PBRT_E_HIP, "no k_path_step instantiation for depth " + std::to_string(ka.depth));
+    if (out) HIPCHK(c, hipMemsetAsync(out->count, 0, sizeof(uint32_t), c->stream));
+    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
+             *paths, in ? *in : pbrt_path_queue{nullptr, nullptr}, out ? *out : pbrt_path_queue{nullptr, nullptr},
+             step ? *step : pbrt_path_step_soa{}, c->d_qrec.get());
     HIPCHK(c, hipGetLastError());
     return PBRT_OK;
 }
@@ -2413,7 +2472,7 @@ extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
 // kernel the library compiles, spelled as its explicit instantiation is
 // (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
-// k_paths_ci, k_paths_cam[_stack], k_li and k_li_direct families are named by their selectors' tables.
+// k_paths_ci, k_paths_cam[_stack], k_li, k_li_direct and k_path_step families are named by their selectors' tables.
 namespace {
 const KernelName kKernelNames[] = {
     // k_paths_m.hip, k_paths_x.hip
@@ -2477,6 +2536,8 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_film_add_tiles<true>),
     PBRT_KERNEL_NAME(k_film_add_merge),
     PBRT_KERNEL_NAME(k_film_rgba8),
+    // k_path_step.hip
+    PBRT_KERNEL_NAME(k_path_begin),
 };
 
 template <class F>
@@ -2486,6 +2547,7 @@ void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' ta
     for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const LiRow& r : kLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const DirectLiRow& r : kDirectLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const PathStepRow& r : kPathStepKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const KernelName& k : kKernelNames) f(k.fn, k.name);
     size_t nm = 0;
     const KernelName* mk = mesh_bvh_kernel_names(&nm);
@@ -2523,6 +2585,8 @@ extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a,
         fn = reinterpret_cast<const void*>(li_kernel(a[0] != 0, a[1]));
     else if (f == "k_li_direct" && n == 2)
         fn = reinterpret_cast<const void*>(direct_li_kernel(a[0] != 0, a[1]));
+    else if (f == "k_path_step" && n == 2)
+        fn = reinterpret_cast<const void*>(path_step_kernel(a[0] != 0, a[1]));
     return fn ? kernel_name_of(fn, nullptr) : nullptr;
 }
 

@@ -67,6 +67,10 @@ __global__ void k_li(DevScene sc, int max_depth, double rr_threshold, int64_t n,
 // batched DirectLighting.Li over device arrays (pbrt_gpu_direct_li_device): k_li_direct.hip
 template <bool kX, int kDepth>
 __global__ void k_li_direct(DevScene sc, int max_depth, int strategy, int nlev, int64_t n, pbrt_ray_soa rays, pbrt_rng_soa rng, pbrt_radiance_soa out, QueryRec* __restrict__ rec, double* __restrict__ lev);
+// Path.Li one iteration at a time over device path state (pbrt_gpu_path_begin_device, pbrt_gpu_path_step_device): k_path_step.hip
+__global__ void k_path_begin(int64_t n, pbrt_ray_soa rays, pbrt_rng_soa rng, pbrt_path_soa p);
+template <bool kX, int kDepth>
+__global__ void k_path_step(DevScene sc, int max_depth, double rr_threshold, int64_t n, pbrt_path_soa p, pbrt_path_queue in, pbrt_path_queue out, pbrt_path_step_soa st, QueryRec* __restrict__ rec);
 // a frame from public pieces (pbrt_gpu_frame_samples_device, pbrt_gpu_film_add_device, pbrt_gpu_film_rgba8_device): k_film_q.hip
 __global__ void k_frame_samples(const pbrt_camera_desc* __restrict__ cam, pbrtfilm::Layout lay, int64_t px_begin, int ns, int64_t n, pbrt_frame_samples_soa out);
 template <bool kLds>

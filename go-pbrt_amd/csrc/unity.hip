@@ -20,6 +20,7 @@
 #include "k_query.hip"
 #include "k_li.hip"
 #include "k_li_direct.hip"
+#include "k_path_step.hip"
 #include "k_film_q.hip"
 #include "render.hip"
 #include "group.hip"

@@ -72,6 +72,8 @@ def lib():
         abi.declare_direct_li(L)
     if hasattr(L, "pbrt_gpu_film_add_device"):
         abi.declare_frame(L)
+    if hasattr(L, "pbrt_gpu_path_step_device"):
+        abi.declare_path(L)
     abi.declare_launch_log(L)
     abi.declare_probe(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
@@ -460,6 +462,13 @@ HIT_DTYPES = {"hit": np.uint8, "t_max": np.float64, "prim": np.int32, "px": np.f
 RNG_KEYS = ("state", "inc")
 LI_DTYPES = {"r": np.float64, "g": np.float64, "b": np.float64, "state": np.uint64, "draws": np.uint32,
              "rays": np.uint32}
+# pbrt_path_soa's arrays (tmax optional): 141 bytes a path, 133 without tmax
+PATH_DTYPES = {**{k: np.float64 for k in RAY_KEYS + ("tmax", "lr", "lg", "lb", "br", "bg", "bb", "eta_scale")},
+               "state": np.uint64, "inc": np.uint64, "draws": np.uint32, "rays": np.uint32, "bounces": np.int32,
+               "status": np.uint8}
+PATH_BYTES = sum(np.dtype(dt).itemsize for dt in PATH_DTYPES.values())
+# pbrt_path_step_soa's arrays (all optional): the hit's, material, and the term added to L
+STEP_DTYPES = {**HIT_DTYPES, "material": np.int32, "ar": np.float64, "ag": np.float64, "ab": np.float64}
 # frame_samples' outputs (tmax, px, py optional) and film_add's inputs
 SAMPLE_DTYPES = {**{k: np.float64 for k in RAY_KEYS + ("tmax", "pfilm_x", "pfilm_y")}, "state": np.uint64,
                  "inc": np.uint64, "px": np.int32, "py": np.int32}
@@ -844,6 +853,130 @@ class Renderer:
         rs, gs, os_ = _li_soas(self, "direct_li_device", rays, rng, n, out)
         d = abi.direct_li_desc(max_depth, dl_strategy)
         return lib().pbrt_gpu_direct_li_device(self.h, C.byref(d), C.byref(rs), C.byref(gs), n, C.byref(os_))
+
+    # ---- Path.Li one bounce at a time (pbrt_gpu_path_begin_device, pbrt_gpu_path_step_device)
+    def path_buffers(self, n, tmax=False):
+        """The arrays of pbrt_path_soa for n paths as a dict of DeviceBuffers (PATH_DTYPES; tmax only
+        when asked: without it a step's ray has TMax +Inf), uninitialised: path_begin fills them."""
+        return {k: self.buffer(n, dt) for k, dt in PATH_DTYPES.items() if tmax or k != "tmax"}
+
+    def path_queue(self, n):
+        """A pbrt_path_queue for up to n paths: {"index": int32 x n, "count": uint32 x 1}."""
+        return {"index": self.buffer(n, np.int32), "count": self.buffer(1, np.uint32)}
+
+    def _path_soa(self, what, paths, n):
+        unknown = set(paths) - set(PATH_DTYPES)
+        missing = [k for k in PATH_DTYPES if k != "tmax" and paths.get(k) is None]
+        if unknown or missing:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{what}: paths: unknown {sorted(unknown)}, missing {missing}")
+        pb = [(k, paths[k], dt) for k, dt in PATH_DTYPES.items() if paths.get(k) is not None]
+        check_buffers(self, n, pb)
+        return _soa(abi.PathSoA, pb)
+
+    def _path_queue(self, what, q, n):
+        if q is None:
+            return None
+        if set(q) != {"index", "count"} or q["index"] is None or q["count"] is None:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{what}: a queue is {{'index': int32 x n, 'count': uint32 x 1}}")
+        check_buffers(self, n, [(what + ".index", q["index"], np.int32)])
+        check_buffers(self, 1, [(what + ".count", q["count"], np.uint32)])
+        return _soa(abi.PathQueue, [("index", q["index"], np.int32), ("count", q["count"], np.uint32)])
+
+    def path_begin(self, rays, rng, n, paths):
+        """pbrt_gpu_path_begin_device: the fresh state of n paths (L 0, beta 1, eta_scale 1, no
+        bounce, draw or ray, ALIVE) from li_device's rays and rng, into the buffers of paths
+        (path_buffers). Enqueue only. Returns the status."""
+        if not isinstance(rng, dict):
+            rng = dict(zip(RNG_KEYS, tuple(rng)))
+        if set(rng) != set(RNG_KEYS):
+            raise PbrtError(abi.PBRT_E_INVALID, f"path_begin: rng is {RNG_KEYS}")
+        rb = _ray_bufs(rays)
+        gb = [(k, rng[k], np.uint64) for k in RNG_KEYS]
+        check_buffers(self, n, rb + gb)
+        ps = self._path_soa("path_begin", paths, n)
+        rs, gs = _soa(abi.RaySoA, rb), _soa(abi.RngSoA, gb)
+        return lib().pbrt_gpu_path_begin_device(self.h, C.byref(rs), C.byref(gs), n, C.byref(ps))
+
+    def path_step(self, paths, n, in_queue=None, out_queue=None, step=None, max_depth=10,
+                  light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0, integrator=abi.PBRT_INTEGRATOR_PATH):
+        """pbrt_gpu_path_step_device: one iteration of Path.Li for every ALIVE path the call covers:
+        paths 0 .. n-1, or those in_queue names (path_queue; its count is read on the device). The
+        paths that are ALIVE afterwards are appended to out_queue (its count is zeroed first). step:
+        a dict of any of STEP_DTYPES' buffers (the hit's arrays, material, ar/ag/ab), written at the
+        indices of the paths advanced. The desc is li_device's. Enqueue only; a path on which the
+        reference panics is PANICKED with L = 0 and counted in query_status(). Returns the status
+        (PBRT_E_UNSUPPORTED: last_error() says why)."""
+        ps = self._path_soa("path_step", paths, n)
+        qi, qo = self._path_queue("in_queue", in_queue, n), self._path_queue("out_queue", out_queue, n)
+        if qi is not None and qo is not None and (in_queue["index"] is out_queue["index"] or
+                                                  in_queue["count"] is out_queue["count"]):
+            raise PbrtError(abi.PBRT_E_INVALID, "path_step: the in and out queues alias")
+        ss = None
+        if step is not None:
+            unknown = set(step) - set(STEP_DTYPES)
+            if unknown:
+                raise PbrtError(abi.PBRT_E_INVALID, f"path_step: step: unknown {sorted(unknown)}")
+            sb = [(k, step[k], dt) for k, dt in STEP_DTYPES.items() if step.get(k) is not None]
+            check_buffers(self, n, sb)
+            ss = abi.PathStepSoA()
+            ss.hit = _soa(abi.HitSoA, [t for t in sb if t[0] in HIT_DTYPES])
+            for k, b, _ in sb:
+                if k not in HIT_DTYPES:
+                    setattr(ss, k, C.cast(C.c_void_p(b.ptr), dict(abi.PathStepSoA._fields_)[k]))
+        d = abi.li_desc(max_depth, light_strategy, rr_threshold, integrator)
+        ref = lambda s: C.byref(s) if s is not None else None   # noqa: E731
+        return lib().pbrt_gpu_path_step_device(self.h, C.byref(d), C.byref(ps), ref(qi), ref(qo), n, ref(ss))
+
+    def radiance_stepwise(self, rays, state, inc, max_depth=10, **desc):
+        """radiance() composed of path_begin and max_depth path_steps over ping-pong queues: the
+        same arguments (desc: light_strategy, rr_threshold), the same return value (L (n, 3), state,
+        draws, rays), the same bits."""
+        return self._stepwise("radiance_stepwise", rays, state, inc, max_depth, desc, False)[:4]
+
+    def radiance_by_bounce(self, rays, state, inc, max_depth=10, **desc):
+        """radiance_stepwise that also returns the (max_depth, n, 3) array of the terms each step
+        added to L (0 where a path was not advanced): (L, state, draws, rays, added). Their sum in
+        step order, as float64 additions from 0, is L."""
+        return self._stepwise("radiance_by_bounce", rays, state, inc, max_depth, desc, True)
+
+    def _stepwise(self, what, rays, state, inc, max_depth, desc, by_bounce):
+        rays = np.ascontiguousarray(rays, dtype=np.float64)
+        n = rays.shape[0]
+        if rays.ndim != 2 or rays.shape[1] not in (6, 7) or len(state) != n or len(inc) != n:
+            raise PbrtError(abi.PBRT_E_INVALID, f"{what}: rays (n, 6) or (n, 7), state and inc of n elements")
+        added = np.zeros((max(int(max_depth), 0), n, 3))
+        if n == 0:
+            return np.zeros((0, 3)), np.zeros(0, np.uint64), np.zeros(0, np.uint32), np.zeros(0, np.uint32), added
+        bufs = []
+        try:
+            rb = [self.upload(rays[:, k]) for k in range(rays.shape[1])]
+            gb = [self.upload(np.asarray(a, dtype=np.uint64)) for a in (state, inc)]
+            pb = self.path_buffers(n, tmax=rays.shape[1] == 7)
+            qs = [self.path_queue(n), self.path_queue(n)]
+            bufs = rb + gb + list(pb.values()) + [b for q in qs for b in q.values()]
+            sb = None
+            if by_bounce:
+                sb = {k: self.buffer(n) for k in ("ar", "ag", "ab")}
+                bufs += list(sb.values())
+            self._check(self.path_begin(tuple(rb), tuple(gb), n, pb))
+            for k in range(int(max_depth)):
+                if by_bounce:
+                    for b in sb.values():
+                        b.upload(np.zeros(n))
+                self._check(self.path_step(pb, n, None if k == 0 else qs[k % 2], qs[(k + 1) % 2], sb,
+                                           max_depth=max_depth, **desc))
+                if by_bounce:
+                    added[k] = np.stack([sb[c].download() for c in ("ar", "ag", "ab")], axis=1)
+            if int(max_depth) < 1:   # (the library's refusal, with nothing stepped)
+                self._check(self.path_step(pb, n, max_depth=max_depth, **desc))
+            rc, rec = self.query_status()
+            if rc:
+                raise PbrtError(rc, self.last_error(), rec)
+            got = {k: pb[k].download() for k in ("lr", "lg", "lb", "state", "draws", "rays")}
+        finally:
+            for b in bufs:
+                b.close()
+        return np.stack([got["lr"], got["lg"], got["lb"]], axis=1), got["state"], got["draws"], got["rays"], added
 
     def direct_li_scratch_bytes(self):
         """pbrt_gpu_direct_li_scratch_bytes: the size of direct_li_device's level-record buffer (it

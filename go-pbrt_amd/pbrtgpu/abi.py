@@ -425,6 +425,41 @@ def declare_li(L):
     L.pbrt_gpu_li_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA)]
 
 
+# --------------------------------- Path.Li one bounce at a time (include/pbrt_gpu.h)
+PBRT_PATH_UNUSED, PBRT_PATH_ALIVE, PBRT_PATH_ENDED, PBRT_PATH_PANICKED = 0, 1, 2, 3
+
+
+class PathSoA(C.Structure):
+    """pbrt_path_soa: the loop-carried state of Path.Li per path (device arrays; tmax may be NULL).
+    141 bytes a path, 133 without tmax."""
+    _fields_ = ([(n, C.POINTER(C.c_double)) for n in ("ox", "oy", "oz", "dx", "dy", "dz", "tmax", "lr", "lg", "lb",
+                                                      "br", "bg", "bb", "eta_scale")] +
+                [("state", C.POINTER(C.c_uint64)), ("inc", C.POINTER(C.c_uint64)), ("draws", C.POINTER(C.c_uint32)),
+                 ("rays", C.POINTER(C.c_uint32)), ("bounces", C.POINTER(C.c_int32)), ("status", C.POINTER(C.c_uint8))])
+
+
+class PathQueue(C.Structure):
+    """pbrt_path_queue: n path indices and their count, both on the device."""
+    _fields_ = [("index", C.POINTER(C.c_int32)), ("count", C.POINTER(C.c_uint32))]
+
+
+class PathStepSoA(C.Structure):
+    """pbrt_path_step_soa: what one step surfaces (every pointer optional)."""
+    _fields_ = [("hit", HitSoA), ("material", C.POINTER(C.c_int32)), ("ar", C.POINTER(C.c_double)),
+                ("ag", C.POINTER(C.c_double)), ("ab", C.POINTER(C.c_double))]
+
+
+PATH_SYMBOLS = ("pbrt_gpu_path_begin_device", "pbrt_gpu_path_step_device")
+
+
+def declare_path(L):
+    """ctypes prototypes of pbrt_gpu_path_begin_device and pbrt_gpu_path_step_device (apart, like declare_li)."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_path_begin_device.argtypes = [vp, P(RaySoA), P(RngSoA), C.c_size_t, P(PathSoA)]
+    L.pbrt_gpu_path_step_device.argtypes = [vp, P(LiDesc), P(PathSoA), P(PathQueue), P(PathQueue), C.c_size_t,
+                                            P(PathStepSoA)]
+
+
 class DirectLiDesc(C.Structure):
     """pbrt_direct_li_desc: what pbrt_gpu_direct_li_device needs of a DirectLighting render desc."""
     _fields_ = [("max_depth", C.c_int32), ("dl_strategy", C.c_int32), ("reserved", C.c_int32 * 2)]

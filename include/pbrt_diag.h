@@ -149,6 +149,7 @@ int pbrt_gpu_kernel_names(const char** out, int n);
  *   "k_render_exact" 1: min_waves
  *   "k_li"           2: kx, depth (0, 64)
  *   "k_li_direct"    2: kx, depth (0, 64)
+ *   "k_path_step"    2: kx, depth (0, 64)
  * NULL for any other family or argument count. */
 const char* pbrt_diag_kernel_choice(const char* family, const int* args, int n);
 /* The device's LDS limit per workgroup, the bound of lds_dynamic + lds_static. */

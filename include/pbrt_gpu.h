@@ -552,6 +552,104 @@ typedef struct pbrt_direct_li_desc {
 int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* ctx, const pbrt_direct_li_desc* desc, const pbrt_ray_soa* rays,
                               const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out);
 
+/* ------------------------------------------------ Path.Li, one bounce at a time
+ * pbrt_gpu_li_device with its loop opened: the loop-carried state of Path.Li
+ * (path.go:32-157) as device arrays the caller owns, a call that gives every
+ * path its fresh state, and a call that advances every live path by exactly one
+ * iteration of the loop (path_step, the code k_li runs in registers). Between
+ * two steps the state is the caller's to read, split, regroup or end.
+ *
+ * Path state: every pointer of pbrt_path_soa is a device pointer to n elements
+ * and required, but tmax. 141 bytes a path, 133 without tmax:
+ *   ox..dz, tmax  the ray the next step traces (tmax NULL: +Inf; where present
+ *                 it is read by a step and written with +Inf after a scatter);
+ *                 the ray's time is 0                              48 + 8 B
+ *   lr, lg, lb    the radiance sum so far                              24 B
+ *   br, bg, bb    beta, the path's throughput                          24 B
+ *   eta_scale     Path.Li's etaScale                                    8 B
+ *   state, inc    the PCG32 stream (inc is only read)               8 + 8 B
+ *   draws         PCG32 draws so far (pbrt_radiance_soa's meaning)      4 B
+ *   rays          closest-hit queries | visibility rays << 16           4 B
+ *   bounces       iterations of Path.Li's loop begun                    4 B
+ *   status        PBRT_PATH_*: a zero-filled array is not live          1 B
+ *
+ * pbrt_gpu_path_begin_device writes the state a path has before its first
+ * iteration (one launch, k_path_begin): L = 0, beta = 1, eta_scale = 1, bounces,
+ * draws and rays 0, status ALIVE, the ray and the stream copied from rays and
+ * rng (pbrt_gpu_li_device's arguments; rays->tmax NULL: +Inf).
+ *
+ * pbrt_gpu_path_step_device runs one iteration (one launch, k_path_step) for
+ * every path the call covers whose status is PBRT_PATH_ALIVE; a path of any
+ * other status is skipped and left untouched. in == NULL covers the paths
+ * 0 .. n-1; otherwise the paths in->index[0 .. *in->count - 1], where *in->count
+ * is read on the device (no host synchronisation) and n bounds it and is the
+ * length of every array, the queues' index arrays included. An index outside
+ * 0 .. n-1 is skipped. After its iteration a path is ALIVE with its next ray in
+ * the state, ENDED, or PANICKED: the reference panics in this iteration, lr/lg/lb
+ * are set to 0 (as pbrt_gpu_li_device reports such a ray) and the path is counted
+ * in the context's query record (pbrt_gpu_query_status) under its index, with
+ * its PBRT_PANIC_*. With out != NULL the call first zeroes *out->count on the
+ * stream, then the kernel appends the index of every covered path that is ALIVE
+ * after the step; the order within out is unspecified, the set is determined.
+ * in and out must not share an index or a count array, and the indices of an
+ * in queue are distinct (an out queue's are).
+ *
+ * step (may be NULL, as may every pointer in it) receives, at the index of each
+ * path this call advanced and nowhere else: hit, the closest hit of the
+ * iteration with pbrt_gpu_intersect_device's values for the step's input ray (a
+ * miss's values where the iteration traced nothing because bounces reached
+ * max_depth, and on a traversal panic); material, the material index of the hit
+ * primitive or mesh (-1 on a miss); ar/ag/ab, the term the iteration added to L:
+ * L_after == L_before + added as one float64 addition per channel, and where
+ * the iteration adds nothing added is 0 and L unchanged (a PANICKED path's L is
+ * 0 and its added 0).
+ *
+ * The contract with pbrt_gpu_li_device: begin followed by desc->max_depth steps
+ * leaves every path ENDED or PANICKED, and lr/lg/lb, state, draws and rays are
+ * then the bits pbrt_gpu_li_device writes to r/g/b, state, draws and rays for
+ * the same rays, streams and desc. A path's values depend on its own state
+ * only: never on its index, its lane, the order of a queue or how the caller
+ * partitions the paths over calls.
+ *
+ * desc is pbrt_gpu_li_device's, with its checks, its refusals
+ * (PBRT_E_UNSUPPORTED: DirectLighting, max_depth > 2048, rough glass, an unknown
+ * strategy, a mixed distribution) and its light-distribution buffer, uploaded
+ * only when the strategy differs from the one last uploaded. Ordering and memory
+ * are pbrt_gpu_intersect_device's: both calls only enqueue on the context's
+ * stream and allocate nothing in the steady state; n == 0 is PBRT_OK and
+ * launches nothing. PBRT_E_INVALID, before any device call: a NULL context,
+ * desc, paths or required pointer (of paths, rays, rng, or of a queue that is
+ * given); n > 2^31 - 1; max_depth < 1; reserved != 0; in and out aliased; or a
+ * render in flight (left untouched). */
+enum { PBRT_PATH_UNUSED = 0, PBRT_PATH_ALIVE = 1, PBRT_PATH_ENDED = 2, PBRT_PATH_PANICKED = 3 };
+typedef struct pbrt_path_soa {
+    double *ox, *oy, *oz, *dx, *dy, *dz;
+    double *tmax;            /* may be NULL => +Inf                               */
+    double *lr, *lg, *lb;
+    double *br, *bg, *bb;
+    double *eta_scale;
+    uint64_t *state;
+    const uint64_t *inc;
+    uint32_t *draws;
+    uint32_t *rays;          /* closest | shadow << 16                            */
+    int32_t *bounces;
+    uint8_t *status;         /* PBRT_PATH_*                                       */
+} pbrt_path_soa;
+typedef struct pbrt_path_queue {
+    int32_t* index;          /* n elements                                        */
+    uint32_t* count;         /* one element, on the device                        */
+} pbrt_path_queue;
+typedef struct pbrt_path_step_soa {
+    pbrt_hit_soa hit;        /* every pointer optional, hit.hit included          */
+    int32_t* material;
+    double *ar, *ag, *ab;
+} pbrt_path_step_soa;
+int pbrt_gpu_path_begin_device(pbrt_gpu_ctx* ctx, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng, size_t n,
+                               const pbrt_path_soa* paths);
+int pbrt_gpu_path_step_device(pbrt_gpu_ctx* ctx, const pbrt_li_desc* desc, const pbrt_path_soa* paths,
+                              const pbrt_path_queue* in, const pbrt_path_queue* out, size_t n,
+                              const pbrt_path_step_soa* step);
+
 /* ---------------------------------------------- a frame from public pieces
  * Three enqueue-only calls that, with pbrt_gpu_li_device between the first two,
  * build a frame on the device: samples, Li, film, RGBA8. The composed film is a

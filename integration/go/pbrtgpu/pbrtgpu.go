@@ -578,6 +578,166 @@ func (r *Renderer) DirectLiDevice(rays DeviceRays, rng DeviceRNG, n int, maxDept
 	return nil
 }
 
+// Path statuses of DevicePaths.Status (PBRT_PATH_*): a zero-filled array is not live.
+const (
+	PathUnused   = uint8(C.PBRT_PATH_UNUSED)
+	PathAlive    = uint8(C.PBRT_PATH_ALIVE)
+	PathEnded    = uint8(C.PBRT_PATH_ENDED)
+	PathPanicked = uint8(C.PBRT_PATH_PANICKED)
+)
+
+// DevicePaths is the loop-carried state of Path.Li per path (pbrt_path_soa), 141
+// bytes a path (133 without TMax): the next ray (float64; TMax may be nil: +Inf),
+// the radiance sum Lr/Lg/Lb, the throughput Br/Bg/Bb and EtaScale (float64), the
+// PCG32 stream State and Inc (uint64), Draws and Rays (uint32: closest | shadow <<
+// 16), Bounces (int32) and Status (uint8).
+type DevicePaths struct {
+	Ox, Oy, Oz, Dx, Dy, Dz, TMax             *DeviceBuffer
+	Lr, Lg, Lb, Br, Bg, Bb, EtaScale         *DeviceBuffer
+	State, Inc, Draws, Rays, Bounces, Status *DeviceBuffer
+}
+
+// DevicePathQueue names paths by index (pbrt_path_queue): Index holds n int32,
+// Count one uint32, both on the device.
+type DevicePathQueue struct{ Index, Count *DeviceBuffer }
+
+// DevicePathStep is what a step surfaces at the index of each path it advanced
+// (pbrt_path_step_soa); every buffer may be nil: the iteration's closest hit,
+// the hit's material index (int32, -1 on a miss) and the term added to L (float64).
+type DevicePathStep struct {
+	Hit        DeviceHits
+	Material   *DeviceBuffer
+	Ar, Ag, Ab *DeviceBuffer
+}
+
+func (r *Renderer) pathSoA(paths DevicePaths, n int) (C.pbrt_path_soa, error) {
+	var ps C.pbrt_path_soa
+	p := [20]unsafe.Pointer{}
+	elem := [20]int{8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 8, 4, 4, 4, 1}
+	var err error
+	for k, d := range []*DeviceBuffer{paths.Ox, paths.Oy, paths.Oz, paths.Dx, paths.Dy, paths.Dz, paths.TMax,
+		paths.Lr, paths.Lg, paths.Lb, paths.Br, paths.Bg, paths.Bb, paths.EtaScale,
+		paths.State, paths.Inc, paths.Draws, paths.Rays, paths.Bounces, paths.Status} {
+		if p[k], err = r.devPtr(d, n, elem[k], k == 6); err != nil {
+			return ps, err
+		}
+	}
+	ps.ox, ps.oy, ps.oz = (*C.double)(p[0]), (*C.double)(p[1]), (*C.double)(p[2])
+	ps.dx, ps.dy, ps.dz = (*C.double)(p[3]), (*C.double)(p[4]), (*C.double)(p[5])
+	ps.tmax = (*C.double)(p[6])
+	ps.lr, ps.lg, ps.lb = (*C.double)(p[7]), (*C.double)(p[8]), (*C.double)(p[9])
+	ps.br, ps.bg, ps.bb = (*C.double)(p[10]), (*C.double)(p[11]), (*C.double)(p[12])
+	ps.eta_scale = (*C.double)(p[13])
+	ps.state, ps.inc = (*C.uint64_t)(p[14]), (*C.uint64_t)(p[15])
+	ps.draws, ps.rays = (*C.uint32_t)(p[16]), (*C.uint32_t)(p[17])
+	ps.bounces, ps.status = (*C.int32_t)(p[18]), (*C.uint8_t)(p[19])
+	return ps, nil
+}
+
+// PathBeginDevice enqueues the fresh state of n paths (pbrt_gpu_path_begin_device):
+// L 0, beta 1, EtaScale 1, no bounce, draw or ray, PathAlive, the ray and the
+// stream copied from LiDevice's rays and rng.
+func (r *Renderer) PathBeginDevice(rays DeviceRays, rng DeviceRNG, n int, paths DevicePaths) error {
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return err
+	}
+	var gs C.pbrt_rng_soa
+	st, err := r.devPtr(rng.State, n, 8, false)
+	if err != nil {
+		return err
+	}
+	inc, err := r.devPtr(rng.Inc, n, 8, false)
+	if err != nil {
+		return err
+	}
+	gs.state, gs.inc = (*C.uint64_t)(st), (*C.uint64_t)(inc)
+	ps, err := r.pathSoA(paths, n)
+	if err != nil {
+		return err
+	}
+	if rc := C.pbrt_gpu_path_begin_device(r.ctx, &soa, &gs, C.size_t(n), &ps); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_path_begin_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+func (r *Renderer) pathQueue(q *DevicePathQueue, n int) (C.pbrt_path_queue, error) {
+	var pq C.pbrt_path_queue
+	idx, err := r.devPtr(q.Index, n, 4, false)
+	if err != nil {
+		return pq, err
+	}
+	cnt, err := r.devPtr(q.Count, 1, 4, false)
+	if err != nil {
+		return pq, err
+	}
+	pq.index, pq.count = (*C.int32_t)(idx), (*C.uint32_t)(cnt)
+	return pq, nil
+}
+
+// PathStepDevice enqueues one iteration of Path.Li's loop for every PathAlive
+// path the call covers (pbrt_gpu_path_step_device): paths 0 .. n-1 when in is
+// nil, else those in names (its count is read on the device). The paths that are
+// alive afterwards are appended to out (nil: no queue; its count is zeroed
+// first). step may be nil. After PathBeginDevice and maxDepth steps every path
+// has ended and Lr/Lg/Lb, State, Draws and Rays are LiDevice's outputs, bit for
+// bit. A path on which the reference panics is PathPanicked with L = 0 and counted
+// in QueryStatus' record. LiDevice's refusals apply; in and out must not alias.
+func (r *Renderer) PathStepDevice(paths DevicePaths, in, out *DevicePathQueue, n int, maxDepth int32,
+	rrThreshold float64, strategy int32, step *DevicePathStep) error {
+	ps, err := r.pathSoA(paths, n)
+	if err != nil {
+		return err
+	}
+	var qi, qo C.pbrt_path_queue
+	var pi, po *C.pbrt_path_queue
+	if in != nil {
+		if qi, err = r.pathQueue(in, n); err != nil {
+			return err
+		}
+		pi = &qi
+	}
+	if out != nil {
+		if qo, err = r.pathQueue(out, n); err != nil {
+			return err
+		}
+		po = &qo
+	}
+	if in != nil && out != nil && (in.Index == out.Index || in.Count == out.Count) {
+		return fmt.Errorf("pbrtgpu: the in and out queues alias")
+	}
+	var ss C.pbrt_path_step_soa
+	var pss *C.pbrt_path_step_soa
+	if step != nil {
+		h := step.Hit
+		p := [13]unsafe.Pointer{}
+		elem := [13]int{1, 8, 4, 8, 8, 8, 8, 8, 8, 4, 8, 8, 8}
+		for k, d := range []*DeviceBuffer{h.Hit, h.TMax, h.Prim, h.Px, h.Py, h.Pz, h.Nx, h.Ny, h.Nz,
+			step.Material, step.Ar, step.Ag, step.Ab} {
+			if p[k], err = r.devPtr(d, n, elem[k], true); err != nil {
+				return err
+			}
+		}
+		var hs C.pbrt_hit_soa
+		hs.hit, hs.t_max, hs.prim = (*C.uint8_t)(p[0]), (*C.double)(p[1]), (*C.int32_t)(p[2])
+		hs.px, hs.py, hs.pz = (*C.double)(p[3]), (*C.double)(p[4]), (*C.double)(p[5])
+		hs.nx, hs.ny, hs.nz = (*C.double)(p[6]), (*C.double)(p[7]), (*C.double)(p[8])
+		ss.hit = hs
+		ss.material = (*C.int32_t)(p[9])
+		ss.ar, ss.ag, ss.ab = (*C.double)(p[10]), (*C.double)(p[11]), (*C.double)(p[12])
+		pss = &ss
+	}
+	var ld C.pbrt_li_desc
+	ld.integrator, ld.max_depth = C.PBRT_INTEGRATOR_PATH, C.int32_t(maxDepth)
+	ld.light_strategy, ld.reserved = C.int32_t(strategy), 0
+	ld.rr_threshold = C.double(rrThreshold)
+	if rc := C.pbrt_gpu_path_step_device(r.ctx, &ld, &ps, pi, po, C.size_t(n), pss); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_path_step_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
 // CameraRaysDevice writes the camera rays of the pixel window [x0, x1) x [y0, y1)
 // in raster order (pbrt_gpu_camera_rays_device), pFilm = pixel + filmOffset; an
 // IntersectDevice on them needs no host step in between.
