@@ -3,7 +3,7 @@
 // (prepare's for a DirectLighting render, render.hip), the choice of the
 // k_li_direct instantiation and its capped grid, and the size of the level
 // records the kX instantiations keep in global memory.
-// Plain C++ with no dependency on HIP: render.hip passes in what it knows of the
+// Plain C++ with no dependency on HIP: queries.hip passes in what it knows of the
 // context, and tests/direct_li_query_check.cpp compiles this header on its own.
 #pragma once
 
@@ -33,11 +33,11 @@ inline int check_args(bool ctx_ok, const pbrt_direct_li_desc* d, const pbrt_ray_
     if (!ctx_ok) return bad("null context");
     if (!d) return bad("the direct li desc is NULL");
     if (!rays) return bad("rays is NULL");
-    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz) return bad("a ray array is NULL");
+    if (!pbrtli::rays_complete(*rays)) return bad("a ray array is NULL");
     if (!rng) return bad("rng is NULL");
-    if (!rng->state || !rng->inc) return bad("an rng array is NULL");
+    if (!pbrtli::rng_complete(*rng)) return bad("an rng array is NULL");
     if (!out) return bad("out is NULL");
-    if (!out->r || !out->g || !out->b) return bad("a radiance array is NULL");
+    if (!pbrtli::radiance_complete(*out)) return bad("a radiance array is NULL");
     if (n > (size_t)INT32_MAX) return bad("more than 2^31 - 1 rays in one query");
     if (d->max_depth < 1) return bad("max_depth < 1");
     if (d->reserved[0] != 0 || d->reserved[1] != 0) return bad("reserved must be 0");

@@ -2,7 +2,7 @@
 // pbrt_gpu_film_add_device (include/pbrt_gpu.h), and the host side of those
 // calls and of pbrt_gpu_film_rgba8_device that needs no device: the argument
 // checks and the refusals.
-// Plain C++ with no dependency on HIP: render.hip passes in what it knows of the
+// Plain C++ with no dependency on HIP: queries.hip passes in what it knows of the
 // context, the kernels of k_film_q.hip call the layout functions on the device
 // (PBRT_FQ_HD), and tests/film_query_check.cpp compiles this header on its own.
 //

@@ -7,15 +7,6 @@
 
 namespace pbrtk {
 
-struct LiNoCache {   // path_step's bounce-1 cache: never read by path_step<2>
-    SI si;
-    BSDF b;
-    BSDFX x;
-    V3 wo;
-    Spec ld[1];
-    int ld_panic[1];
-};
-
 // paths_cam's lane refill (k_paths_c.hip) with the camera taken out: a wave owns
 // the kLiRays rays from blockIdx.x * kLiRays on; an idle lane takes the next of
 // them by its rank in the idle ballot (so a refill's loads are contiguous),
@@ -43,7 +34,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
     const int64_t i0 = (int64_t)blockIdx.x * pbrtli::kLiRays;
     const int T = (int)(n - i0 < (int64_t)pbrtli::kLiRays ? n - i0 : (int64_t)pbrtli::kLiRays);   // > 0 by the grid
     const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
-    LiNoCache none;   // (never read: no code is generated for it)
+    NoCache none;   // (never read: no code is generated for it)
     int base = 0;
     int w = -1;
     PathStateLds ps;
@@ -99,10 +90,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
                 if (out.state) out.state[i] = c.rng.state;
                 if (out.draws) out.draws[i] = c.draws;
                 if (out.rays) out.rays[i] = *ps.rays;
-                if (pnc) {
-                    atomicAdd(&rec->panics, 1ull);
-                    atomicMin(&rec->first, ((unsigned long long)i << 8) | (unsigned long long)(pnc & 0xFF));
-                }
+                if (pnc) query_panic(rec, i, pnc);
                 w = -1;
             }
         }

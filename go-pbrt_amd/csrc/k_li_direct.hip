@@ -194,10 +194,7 @@ __global__ __launch_bounds__(kWave) void k_li_direct(DevScene sc, int max_depth,
                     if (out.state) out.state[i] = c.rng.state;
                     if (out.draws) out.draws[i] = c.draws;
                     if (out.rays) out.rays[i] = closest * kRayClosest + (uint32_t)shadow * kRayShadow;
-                    if (panic) {
-                        atomicAdd(&rec->panics, 1ull);
-                        atomicMin(&rec->first, ((unsigned long long)i << 8) | (unsigned long long)(panic & 0xFF));
-                    }
+                    if (panic) query_panic(rec, i, panic);
                     w = -1;
                 }
             }

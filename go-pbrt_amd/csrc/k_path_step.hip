@@ -8,15 +8,6 @@
 
 namespace pbrtk {
 
-struct StepNoCache {   // path_step's bounce-1 cache: never read by path_step<2>
-    SI si;
-    BSDF b;
-    BSDFX x;
-    V3 wo;
-    Spec ld[1];
-    int ld_panic[1];
-};
-
 // path_step's State of k_path_step: PathState without the radiance sum, which an
 // iteration only adds to, once, as its last statement; the term is kept instead
 // (kTapAdded) and the sum stays in memory until the iteration is over. note_hit
@@ -106,7 +97,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
     const int lane = threadIdx.x;
     const int T = (int)(cnt - e0 < (int64_t)pbrtpath::kSlice ? cnt - e0 : (int64_t)pbrtpath::kSlice);
     const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
-    StepNoCache none;   // (never read: no code is generated for it)
+    NoCache none;   // (never read: no code is generated for it)
     const SpecSampler ss{nullptr, 1, 0, nullptr};
     for (int t0 = 0; t0 < T; t0 += kWave) {   // uniform
         const int t = t0 + lane;
@@ -153,8 +144,7 @@ __global__ __launch_bounds__(kWave) __attribute__((amdgpu_waves_per_eu(kPathsWav
                 p.lr[i] = 0.0;
                 p.lg[i] = 0.0;
                 p.lb[i] = 0.0;
-                atomicAdd(&rec->panics, 1ull);
-                atomicMin(&rec->first, ((unsigned long long)i << 8) | (unsigned long long)(pnc & 0xFF));
+                query_panic(rec, i, pnc);
             } else if (ps.flags & kTapAdded) {
                 added = ps.added;
                 p.lr[i] = p.lr[i] + added.r;

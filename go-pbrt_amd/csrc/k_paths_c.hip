@@ -60,14 +60,6 @@ struct CamMeta {
     uint64_t inc, tile;
     int32_t nv, cum, px, py;
 };
-struct CamNoCache {   // path_step's bounce-1 cache: never read by path_step<2>
-    SI si;
-    BSDF b;
-    BSDFX x;
-    V3 wo;
-    Spec ld[1];
-    int ld_panic[1];
-};
 
 template <int P, bool kMB, int kDepth>
 __device__ __forceinline__ void paths_cam(DevScene sc, const RenderParams& rp, const WaveBufs& wb, int64_t slot_base,
@@ -117,7 +109,7 @@ __device__ __forceinline__ void paths_cam(DevScene sc, const RenderParams& rp, c
     const unsigned long long lt_mask = (1ULL << lane) - 1ULL;
     const int T = meta[P].cum;
     const pbrt_camera_desc& cam = *sc.camera;
-    CamNoCache none;   // (never read: no code is generated for it)
+    NoCache none;   // (never read: no code is generated for it)
     int base = 0;
     int w = -1, j = 0, k = 0;
     PathStateLds ps;

@@ -53,10 +53,7 @@ __device__ __forceinline__ void query_hit_lane(const DevScene& sc, int64_t n, co
         if (hits.ny) hits.ny[i] = si.n.y;
         if (hits.nz) hits.nz[i] = si.n.z;
     }
-    if (panic) {
-        atomicAdd(&rec->panics, 1ull);
-        atomicMin(&rec->first, ((unsigned long long)i << 8) | (unsigned long long)(panic & 0xFF));
-    }
+    if (panic) query_panic(rec, i, panic);
 }
 
 template <bool kAny, bool kMeshOnly>

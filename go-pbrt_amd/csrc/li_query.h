@@ -2,7 +2,7 @@
 // needs no device: the argument checks, the conditions under which path_step is
 // not the reference (wave_eligible's, render.hip), and the choice of the k_li
 // instantiation and its grid from the scene.
-// Plain C++ with no dependency on HIP: render.hip passes in what it knows of
+// Plain C++ with no dependency on HIP: queries.hip passes in what it knows of
 // the context, and tests/li_query_check.cpp compiles this header on its own.
 #pragma once
 
@@ -16,6 +16,14 @@ namespace pbrtli {
 constexpr int kLiRays = 256;        // rays of one wave's work list (k_li)
 constexpr int kLiMaxDepth = 2048;   // draws of a path < 2^32 (wave_eligible)
 
+// Every array a query requires of its rays (tmax may be NULL), its rng and its
+// radiance: the one test each for every query that takes them (a caller words
+// its own refusal). R: pbrt_ray_soa, or the camera rays' pbrt_ray_soa_out.
+template <class R>
+inline bool rays_complete(const R& r) { return r.ox && r.oy && r.oz && r.dx && r.dy && r.dz; }
+inline bool rng_complete(const pbrt_rng_soa& g) { return g.state && g.inc; }
+inline bool radiance_complete(const pbrt_radiance_soa& o) { return o.r && o.g && o.b; }
+
 // PBRT_E_INVALID's conditions, in the header's order; `why` names the first.
 // ctx_ok: the context is not NULL. in_flight: a render is in flight on it.
 inline int check_args(bool ctx_ok, const pbrt_li_desc* d, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng, size_t n,
@@ -27,11 +35,11 @@ inline int check_args(bool ctx_ok, const pbrt_li_desc* d, const pbrt_ray_soa* ra
     if (!ctx_ok) return bad("null context");
     if (!d) return bad("the li desc is NULL");
     if (!rays) return bad("rays is NULL");
-    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz) return bad("a ray array is NULL");
+    if (!rays_complete(*rays)) return bad("a ray array is NULL");
     if (!rng) return bad("rng is NULL");
-    if (!rng->state || !rng->inc) return bad("an rng array is NULL");
+    if (!rng_complete(*rng)) return bad("an rng array is NULL");
     if (!out) return bad("out is NULL");
-    if (!out->r || !out->g || !out->b) return bad("a radiance array is NULL");
+    if (!radiance_complete(*out)) return bad("a radiance array is NULL");
     if (n > (size_t)INT32_MAX) return bad("more than 2^31 - 1 rays in one query");
     if (d->max_depth < 1) return bad("max_depth < 1");
     if (d->reserved != 0) return bad("reserved must be 0");

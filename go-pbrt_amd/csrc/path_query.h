@@ -4,7 +4,7 @@
 // What the desc and the scene refuse, the light distributions served and the
 // choice of the instantiation are the li query's (li_query.h: check_supported,
 // check_distribution, kernel_args), used as they are.
-// Plain C++ with no dependency on HIP: render.hip passes in what it knows of
+// Plain C++ with no dependency on HIP: queries.hip passes in what it knows of
 // the context, and tests/path_query_check.cpp compiles this header on its own.
 #pragma once
 
@@ -42,9 +42,9 @@ inline int check_begin(bool ctx_ok, const pbrt_ray_soa* rays, const pbrt_rng_soa
     };
     if (!ctx_ok) return bad("null context");
     if (!rays) return bad("rays is NULL");
-    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz) return bad("a ray array is NULL");
+    if (!pbrtli::rays_complete(*rays)) return bad("a ray array is NULL");
     if (!rng) return bad("rng is NULL");
-    if (!rng->state || !rng->inc) return bad("an rng array is NULL");
+    if (!pbrtli::rng_complete(*rng)) return bad("an rng array is NULL");
     if (!paths) return bad("paths is NULL");
     if (!state_complete(*paths)) return bad("a path state array is NULL");
     if (n > (size_t)INT32_MAX) return bad("more than 2^31 - 1 paths in one call");

@@ -206,6 +206,16 @@ __device__ __forceinline__ void add_rays(PathStateLds& s, uint32_t v) { *s.rays 
 // another unit that surfaces the interaction has its own (k_path_step.hip).
 __device__ __forceinline__ void note_hit(PathState&, const DevScene&, const SI&) {}
 __device__ __forceinline__ void note_hit(PathStateLds&, const DevScene&, const SI&) {}
+// path_step's Cache of a kernel that runs path_step<2> only (k_paths_cam, k_li,
+// k_path_step): the bounce-1 cache is never read, and no code is generated for it.
+struct NoCache {
+    SI si;
+    BSDF b;
+    BSDFX x;
+    V3 wo;
+    Spec ld[1];
+    int ld_panic[1];
+};
 // kWhich: 0 any iteration, 1 only the first (s.first == 1: bounce 1 from the
 // pixel cache, no traversal), 2 only later ones (s.first == 0).
 //

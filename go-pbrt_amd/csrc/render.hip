@@ -1,8 +1,22 @@
-// render.hip — host side of the MI355X (gfx950) library: scene upload, launch
-// planning and the C ABI of include/pbrt_gpu.h.
-//
-// Kernels (each family in its own translation unit, k_*.hip; declarations in
-// render_kernels.h, shared types and helpers in render_common.h)
+// render.hip — a context's life and its frame: scene upload (pbrt_gpu_create),
+// launch planning and the frame's stages (render_enqueue, pbrt_gpu_synchronize),
+// the film's way out. The host side of the MI355X (gfx950) library by unit:
+//   context.h          what every unit below needs: HIPCHK, DevBuf, pbrt_gpu_ctx,
+//                      set_err, launch_k, dev_scene, with_slot, query_blocked
+//   kernel_select.hip  the selectors (kernel_select.h: arguments in, the host
+//                      pointer of that instantiation out) and the launch log's names
+//   render.hip         create / destroy / cancel / last_error; eligibility and LDS
+//                      layouts, prepare, the frame's stages, synchronize, render;
+//                      film_download, pbrt_film_to_rgba8, the group's member view
+//   queries.hip        everything a context answers between frames: ray queries,
+//                      camera rays, Li / DirectLighting.Li / Path.Li by steps, a
+//                      frame from public pieces, the context's buffers
+//   diag.hip           include/pbrt_diag.h's read-outs: k_probe, counters, mesh,
+//                      schedule records, launch log, build id, ABI sizes
+//   group.hip          device groups over member contexts (group.h)
+//   mesh_bvh.hip       the device LBVH build of the mesh extension
+// The kernels are each family's own unit (k_*.hip; declarations in
+// render_kernels.h, shared types and helpers in render_common.h). A frame's:
 //   k_render_exact   EXACT mode: one lane per 16-px tile. The lane replays the
 //                    tile's PCG32 stream exactly as pbrt.Render's worker does
 //                    (integrator.go:228-289, 311-340): pixel loop, Stratified
@@ -23,9 +37,6 @@
 //                    lane per sample.
 //   k_merge_film     Film.MergeFilmTile (film.go:115-132): per output pixel,
 //                    RGBToXYZ of every covering tile film in tile-index order.
-//   k_intersect[_p]  batch BVH closest-hit / any-hit (bvh.go:659-765).
-//   k_query_*        the same over SoA arrays resident on the device, and the
-//                    camera rays of a pixel window (pbrt_gpu_*_device).
 //
 // Everything is float64 with -ffp-contract=off (bit parity with the Go
 // reference). The scene is a few KB and is read through the scalar/vector L1.
@@ -45,14 +56,8 @@
 #include "../../include/pbrt_gpu.h"
 #include "../../include/pbrt_diag.h"
 #include "../../include/pbrt_scene.h"
-#include "knobs.h"
-#include "mesh_bvh.h"
-#include "li_query.h"
-#include "direct_li_query.h"
-#include "path_query.h"
-#include "film_query.h"
-#include "query_buffers.h"
-#include "render_kernels.h"
+#include "context.h"
+#include "kernel_select.h"
 #include "scene_tables.h"
 #include "schedule.h"
 
@@ -68,234 +73,6 @@ constexpr int kTickPlanes = 3;   // durations, start clocks, end clocks
 #else
 constexpr int kTickPlanes = 1;
 #endif
-
-namespace {
-int set_err(pbrt_gpu_ctx* c, int code, const std::string& m);
-}
-#define HIPCHK(ctx, call)                                                                            \
-    do {                                                                                             \
-        hipError_t e_ = (call);                                                                      \
-        if (e_ != hipSuccess)                                                                        \
-            return set_err(ctx, PBRT_E_HIP, std::string(#call ": ") + hipGetErrorString(e_));      \
-    } while (0)
-
-// The one owner of a device allocation: freed with its owner (the context, or a
-// scope). Errors go to the context `c` (null outside one).
-template <class T>
-class DevBuf {
-  public:
-    DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
-    DevBuf& operator=(DevBuf&& o) noexcept {
-        std::swap(p_, o.p_);
-        std::swap(cap_, o.cap_);
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    T* get() const { return p_; }
-    size_t cap() const { return cap_; }   // elements it has room for
-    // room for n elements: kept if it has them, else freed and allocated anew (the contents are lost)
-    int ensure(pbrt_gpu_ctx* c, size_t n) {
-        if (cap_ >= n && p_) return PBRT_OK;
-        release();
-        HIPCHK(c, hipMalloc((void**)&p_, sizeof(T) * (n ? n : 1)));
-        cap_ = n;
-        return PBRT_OK;
-    }
-    // a fresh allocation of n elements (an empty array keeps a valid pointer), filled from src unless null
-    int upload(pbrt_gpu_ctx* c, const T* src, size_t n) {
-        if (n == 0) n = 1;
-        release();
-        HIPCHK(c, hipMalloc((void**)&p_, sizeof(T) * n));
-        cap_ = n;
-        if (src) HIPCHK(c, hipMemcpy(p_, src, sizeof(T) * n, hipMemcpyHostToDevice));
-        return PBRT_OK;
-    }
-
-  private:
-    void release() {
-        if (p_) (void)hipFree(p_);
-        p_ = nullptr;
-        cap_ = 0;
-    }
-    T* p_ = nullptr;
-    size_t cap_ = 0;   // elements
-};
-
-struct pbrt_gpu_ctx {
-    Knobs knobs;
-    int device = 0;
-    struct {
-        int n_simd = 1024;                 // SIMDs of the device (4 per CU)
-        size_t lds_per_block = 65536;      // the device's LDS limit per workgroup (sharedMemPerBlock)
-        size_t lds_per_cu = 160 * 1024;    // LDS of a CU (maxSharedMemoryPerMultiProcessor)
-    } dev;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
-    // heavy/light split of k_chain_ci: the heaviest tiles with 4 waves each on
-    // the main stream, the rest on stream2, concurrently
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev_split = nullptr, ev_join = nullptr;
-    // PBRT_PATHS_OVERLAP: a high-priority stream for the light chain launch, the
-    // events of the completion-driven path stage, and k_chain_ci's progress record
-    // (layout at kProgHead)
-    struct {
-        hipStream_t stream3 = nullptr;
-        hipEvent_t ev_l2 = nullptr, ev_p1 = nullptr;
-        int64_t done = 0;                // slots whose path stage was launched beside the chains
-        DevBuf<uint32_t> d_prog;
-        // a frame whose k_gate saw the chains stand still (a dispatcher that serialises
-        // kernels across streams) is rendered again without the overlap; two such
-        // frames in a row turn the overlap off for the context
-        pbrt_render_desc last_rd{};
-        double* last_film_device = nullptr;
-        int stalls = 0;
-        bool retry = false;
-    } ov;
-    MeshBuild mesh;                // triangle meshes + their LBVH (extension)
-    // k_chain_ci heaviest-first schedule: per-slot chain time of the last
-    // EXACT frame (wall_clock64 ticks) and the slot order derived from it
-    struct {
-        int64_t heavy_k = 0;                 // slots at the front of h_slot_order that get 4 waves
-        int ci_wps = 2;                      // waves/SIMD of the last one-wave k_chain_ci launch (3 or 2)
-        int64_t last_heavy = 0;              // heavy slots of the last EXACT launch (0: no split)
-        std::vector<uint32_t> h_last_ticks;  // per-slot chain ticks of the last EXACT frame
-        std::vector<uint8_t> h_slot_kw;      // waves per tile each slot ran with in the last frame
-        DevBuf<uint32_t> d_ticks;            // [kTickPlanes][slots]
-        std::vector<uint32_t> h_tick_clocks; // diagnostics builds: [start | end] clocks of the last frame
-        DevBuf<uint32_t> d_slot_order;
-        std::vector<uint32_t> h_slot_order;
-        uint64_t order_key = 0, ticks_key = 0;
-        int64_t ticks_n = 0;
-        bool ticks_pending = false;
-        int src = 0;                         // schedule of the last EXACT frame: PBRT_SCHED_* (pbrt_diag.h)
-        // cold-frame schedule (k_tile_cost): per-slot features and sort keys
-        DevBuf<float> d_cost;
-        DevBuf<uint64_t> d_cost_keys;
-        int64_t cost_n = 0;
-        bool probed = false;                 // the last EXACT frame ran the cost probe
-    } sched;
-    uint64_t scene_hash = 0;         // content hash of the scene (process-wide schedule cache)
-    double* film_target = nullptr;   // caller buffer of the last render_async_into
-    int lanes_per_wave = 64;
-    bool lanes_per_wave_set = false;
-    int min_waves = 1;      // amdgpu_waves_per_eu variant of k_render_exact
-    int occ_req = 0;        // opts.occupancy as given (0 = each kernel's default)
-    int kernel_req = PBRT_KERNEL_AUTO;
-    int last_kernel = 0;    // PBRT_KERNEL_SERIAL / PBRT_KERNEL_WAVE
-    DevBuf<PcgJump> d_jump;
-    pbrt_distribution_desc host_dist;
-    // wave-parallel path (k_wf_primary, k_chain_ci, k_paths_ci / k_pw_*, k_film)
-    ChainLayout lay{};
-    bool use_spec = false;
-    DevBuf<unsigned char> d_wave;      // per-batch pixel records, stratified values, RNG states, L
-    int64_t wave_batch = 0;            // tile slots per batch
-    int tiles_per_wave = 1;            // k_chain_ci lane groups per wave (64 / lanes per tile)
-    std::vector<hipEvent_t> bev;       // per batch: before the chain, after the chain, after the paths
-    int n_batches = 0;
-    WaveBufs wb{};
-    bool use_ci = false;   // the Path chain stage (k_chain_ci)
-    bool use_dl = false;   // DirectLighting on k_dl_setup / k_dl_samples
-    ChainLayout lay_ci{};
-    bool use_cam = false;   // the camera-start route (PBRT_KERNEL_WAVE_CAM: k_chain_cam, k_paths_cam, k_film_cam)
-    ChainLayout lay_cam{};
-    // device scene
-    DevBuf<pbrt_shape_desc> d_shapes;
-    DevBuf<pbrt_material_desc> d_materials;
-    DevBuf<pbrt_primitive_desc> d_prims;
-    DevBuf<DevNode> d_nodes;
-    DevBuf<uint32_t> d_order;        // [8][n_nodes] preorder visit tables, then [8][n_nodes] leaf lists (dev_order)
-    DevBuf<double> d_groups;         // leaf culling groups (cull_groups)
-    DevBuf<uint32_t> d_gmasks;
-    int n_groups = 0;
-    std::vector<int> h_node_prims;   // nPrimitives per node (leaf count for DevScene)
-    DevBuf<DevPrim> d_fprims;
-    DevBuf<pbrt_light_desc> d_lights;
-    DevBuf<pbrt_camera_desc> d_camera;
-    DevBuf<pbrt_film_desc> d_film;
-    DevBuf<pbrt_distribution_desc> d_dist;
-    pbrt_scene_desc host_scene;   // counts + film/camera (pointer fields are not kept)
-    std::vector<pbrt_light_desc> host_lights;
-    bool non_matte = false;       // Mirror, Glass or OrenNayar material: kX wave kernels or the serial kernel
-    bool rough_glass = false;     // a Glass material with roughness: serial kernel only
-    // per-render buffers (grown on demand)
-    DevBuf<double> d_films;
-    DevBuf<double> d_s1d;
-    DevBuf<PanicRec> d_panics;
-    DevBuf<Counters> d_ctr;
-    // path wavefront (k_pw_*, PBRT_PATHS_WF=1): path records, queues, counters,
-    // bounce-1 light estimates, per-pixel panic keys (grown on demand)
-    DevBuf<unsigned char> d_pw;
-    DevBuf<double> d_out;
-    // last render
-    RenderParams rp{};
-    bool rendered = false;
-    // cancellation (pbrt_gpu_cancel): a flag in fine-grained host memory the
-    // kernels poll; it belongs to the render in flight (render_async entry to
-    // synchronize) and is cleared when that render ends, so a cancel never
-    // outlives its render and never reaches the next one
-    struct {
-        std::mutex mu;
-        bool in_flight = false;
-        bool req = false;
-        int* h_flag = nullptr;   // hipHostMalloc (coherent, mapped)
-        int* d_flag = nullptr;   // its device address
-        DevBuf<int> d_seen;      // device-memory copy the kernels publish (reset per render)
-        // A render begins (in_flight_now) or has ended: the flag is cleared either
-        // way. Returns whether the render that was in flight had been cancelled.
-        bool reset(bool in_flight_now) {
-            std::lock_guard<std::mutex> lk(mu);
-            const bool cancelled = in_flight && req;
-            in_flight = in_flight_now;
-            req = false;
-            __atomic_store_n(h_flag, 0, __ATOMIC_SEQ_CST);
-            return cancelled;
-        }
-    } cancel;
-    // device-resident queries: the buffers the context owns (pbrt_gpu_buffer;
-    // whatever is left is freed by pbrt_gpu_destroy) and the panic record of
-    // the queries since the last pbrt_gpu_query_status (allocated by the first)
-    pbrtq::BufferList qbufs;
-    DevBuf<QueryRec> d_qrec;
-    // pbrt_gpu_li_device: the light distribution of the strategy last queried, in a buffer of the
-    // query's own (a frame uploads its strategy's to d_dist), uploaded when the strategy changes
-    struct {
-        DevBuf<pbrt_distribution_desc> d_dist;
-        pbrt_distribution_desc host_dist;
-        int strategy = 0;   // the strategy d_dist holds (0: none yet)
-    } li;
-    // pbrt_gpu_direct_li_device: the level records of k_li_direct<true, *>, [workgroup][level][field][lane]
-    // (grown on demand; sized by the capped grid and max_depth, direct_li_query.h)
-    DevBuf<double> d_dli_levels;
-    // pbrt_gpu_film_add_device: the tile films of a call's tile range (grown on demand)
-    DevBuf<double> d_fq_films;
-    // every kernel launch of the context (pbrt_gpu_launch_log): the last frame's
-    // (cleared by render_enqueue) and those outside a frame (LBVH build, queries)
-    LaunchLog log_frame, log_aux;
-    bool in_frame = false;
-    std::string err;
-    std::chrono::steady_clock::time_point t_start;
-};
-
-namespace {
-
-// the process cache's key (schedule.h) of a schedule key on this context's scene and device
-uint64_t sched_cache_key(const pbrt_gpu_ctx* c, uint64_t skey) {
-    uint64_t h = fnv_bytes(c->scene_hash, &skey, sizeof(skey));
-    return fnv_bytes(h, &c->dev.n_simd, sizeof(c->dev.n_simd));   // the device's size shapes the split
-}
-
-int set_err(pbrt_gpu_ctx* c, int code, const std::string& m) {
-    if (c) c->err = m;
-    return code;
-}
-
-// Every launch of a context: the record (launch_log.h), then hipLaunchKernelGGL.
-template <class... P, class... A>
-void launch_k(pbrt_gpu_ctx* c, void (*kern)(P...), dim3 grid, dim3 block, unsigned lds, hipStream_t st, A&&... args) {
-    const int sid = st == c->stream ? 0 : st == c->stream2 ? 2 : 3;
-    launch_logged(c->in_frame ? &c->log_frame : &c->log_aux, sid, kern, grid, block, lds, st, std::forward<A>(args)...);
-}
 
 DevScene dev_scene(const pbrt_gpu_ctx* c, bool with_dist) {
     DevScene s;
@@ -327,13 +104,12 @@ DevScene dev_scene(const pbrt_gpu_ctx* c, bool with_dist) {
     return s;
 }
 
-// The scene view a launch passes, tagged with its kernel's counter set for
-// the mesh-traversal counting build (PBRT_MESH_COUNT; ignored otherwise):
-// 1 k_wf_primary, 2 k_chain_ci, 3 k_paths_ci / k_pw_* EXACT, 4 k_mb_setup,
-// 5 k_paths_ci / k_pw_* THROUGHPUT, 6 k_render_exact, 7 k_intersect.
-DevScene with_slot(DevScene s, int slot) {
-    s.mesh.count_slot = slot;
-    return s;
+namespace {
+
+// the process cache's key (schedule.h) of a schedule key on this context's scene and device
+uint64_t sched_cache_key(const pbrt_gpu_ctx* c, uint64_t skey) {
+    uint64_t h = fnv_bytes(c->scene_hash, &skey, sizeof(skey));
+    return fnv_bytes(h, &c->dev.n_simd, sizeof(c->dev.n_simd));   // the device's size shapes the split
 }
 
 std::vector<DevNode> dev_nodes(const pbrt_scene_desc* s) {
@@ -546,132 +322,6 @@ ChainLayout ci_layout(const ChainLayout& base, int w, int G, unsigned& lds_bytes
     lds_bytes = (unsigned)l.pcs + (unsigned)(2 * G * sizeof(ChainCache));
     l.total = (int)lds_bytes;
     return l;
-}
-
-// Kernel selectors, one per templated family: plain arguments in, the host function pointer of
-// exactly that instantiation out, nullptr for a combination no unit compiles. They decide nothing;
-// which arguments a frame asks for is its launch function's policy, and a launch site turns
-// nullptr into PBRT_E_HIP before it launches anything. pbrt_diag_kernel_choice reads them, and
-// tests/test_kernel_selectors.py holds each table equal to the compiled instantiations.
-using ChainKernel = decltype(&k_chain_ci<1>);
-struct ChainRow { int w, depth; bool kx; int eu; bool spwin, multi; ChainKernel fn; const char* name; };
-#define CHAIN_ROW(...) {__VA_ARGS__, &k_chain_ci<__VA_ARGS__>, "k_chain_ci<" #__VA_ARGS__ ">"}
-const ChainRow kChainKernels[] = {
-    // one wave per tile, the group's state in scalar registers (k_chain_1.hip)
-    CHAIN_ROW(1, 0, false, 0, false, false),  CHAIN_ROW(1, 0, false, 2, false, false),
-    CHAIN_ROW(1, 64, false, 0, false, false), CHAIN_ROW(1, 64, false, 2, false, false),
-    CHAIN_ROW(1, 0, false, 0, true, false),   CHAIN_ROW(1, 0, false, 2, true, false),
-    CHAIN_ROW(1, -1, false, 0, false, false),
-    // 2, 4 or 8 waves per tile (k_chain_n.hip)
-    CHAIN_ROW(2, 0, false, 0, false, false),  CHAIN_ROW(4, 0, false, 0, false, false),
-    CHAIN_ROW(8, 0, false, 0, false, false),  CHAIN_ROW(2, 64, false, 0, false, false),
-    CHAIN_ROW(4, 64, false, 0, false, false), CHAIN_ROW(8, 64, false, 0, false, false),
-    CHAIN_ROW(2, 0, false, 0, true, false),   CHAIN_ROW(4, 0, false, 0, true, false),
-    CHAIN_ROW(8, 0, false, 0, true, false),   CHAIN_ROW(2, -1, false, 0, false, false),
-    CHAIN_ROW(4, -1, false, 0, false, false), CHAIN_ROW(8, -1, false, 0, false, false),
-    // kX at 2 or 4 waves per tile (k_chain_x.hip)
-    CHAIN_ROW(2, 0, true, 0, false, false),   CHAIN_ROW(4, 0, true, 0, false, false),
-    CHAIN_ROW(2, 64, true, 0, false, false),  CHAIN_ROW(4, 64, true, 0, false, false),
-    // the per-lane code: several tiles per wave, and the one-wave kX chain (k_chain_g.hip)
-    CHAIN_ROW(1, 0, false, 0, false, true),   CHAIN_ROW(1, 0, false, 2, false, true),
-    CHAIN_ROW(1, 64, false, 0, false, true),  CHAIN_ROW(1, 64, false, 2, false, true),
-    CHAIN_ROW(1, 0, false, 0, true, true),    CHAIN_ROW(1, 0, false, 2, true, true),
-    CHAIN_ROW(1, -1, false, 0, false, true),  CHAIN_ROW(1, 0, true, 0, false, true),
-    CHAIN_ROW(1, 64, true, 0, false, true),
-};
-#undef CHAIN_ROW
-ChainKernel chain_kernel(int w, int depth, bool kx, int eu, bool spwin, bool multi) {
-    for (const ChainRow& r : kChainKernels)
-        if (r.w == w && r.depth == depth && r.kx == kx && r.eu == eu && r.spwin == spwin && r.multi == multi)
-            return r.fn;
-    return nullptr;
-}
-
-using PathsCiKernel = decltype(&k_paths_ci<4>);
-struct PathsCiRow { int P; bool mb, kx; PathsCiKernel fn; const char* name; };
-#define PATHS_CI_ROW(...) {__VA_ARGS__, &k_paths_ci<__VA_ARGS__>, "k_paths_ci<" #__VA_ARGS__ ">"}
-const PathsCiRow kPathsCiKernels[] = {   // (kX: 4 or 8 pixels per wave)
-    PATHS_CI_ROW(2, false, false), PATHS_CI_ROW(4, false, false), PATHS_CI_ROW(8, false, false),
-    PATHS_CI_ROW(2, true, false),  PATHS_CI_ROW(4, true, false),  PATHS_CI_ROW(8, true, false),
-    PATHS_CI_ROW(4, false, true),  PATHS_CI_ROW(8, false, true),
-    PATHS_CI_ROW(4, true, true),   PATHS_CI_ROW(8, true, true),
-};
-#undef PATHS_CI_ROW
-PathsCiKernel paths_ci_kernel(int P, bool mb, bool kx) {
-    for (const PathsCiRow& r : kPathsCiKernels)
-        if (r.P == P && r.mb == mb && r.kx == kx) return r.fn;
-    return nullptr;
-}
-// dynamic LDS of a k_paths_ci<P> workgroup that stages `staged_values` stratified values (-1: no such P)
-int paths_ci_lds(int P, int staged_values) {
-    switch (P) {
-    case 2: return paths_group_lds<2>(staged_values);
-    case 4: return paths_group_lds<4>(staged_values);
-    case 8: return paths_group_lds<8>(staged_values);
-    default: return -1;
-    }
-}
-
-using PathsCamKernel = decltype(&k_paths_cam<4, false>);
-struct PathsCamRow { int P; bool mb, stack; PathsCamKernel fn; const char* name; };
-#define PATHS_CAM_ROWS(P, mb)                                             \
-    {P, mb, false, &k_paths_cam<P, mb>, "k_paths_cam<" #P ", " #mb ">"}, \
-    {P, mb, true, &k_paths_cam_stack<P, mb>, "k_paths_cam_stack<" #P ", " #mb ">"}
-const PathsCamRow kPathsCamKernels[] = {   // stack: the k_paths_cam_stack kernels of trees beyond kLdsNodes
-    PATHS_CAM_ROWS(4, false), PATHS_CAM_ROWS(16, false), PATHS_CAM_ROWS(64, false),
-    PATHS_CAM_ROWS(4, true),  PATHS_CAM_ROWS(16, true),  PATHS_CAM_ROWS(64, true),
-};
-#undef PATHS_CAM_ROWS
-PathsCamKernel paths_cam_kernel(int P, bool mb, bool stack) {
-    for (const PathsCamRow& r : kPathsCamKernels)
-        if (r.P == P && r.mb == mb && r.stack == stack) return r.fn;
-    return nullptr;
-}
-
-using LiKernel = decltype(&k_li<false, 0>);
-struct LiRow { bool kx; int depth; LiKernel fn; const char* name; };
-#define LI_ROW(kx, depth) {kx, depth, &k_li<kx, depth>, "k_li<" #kx ", " #depth ">"}
-const LiRow kLiKernels[] = {LI_ROW(false, 0), LI_ROW(true, 0), LI_ROW(false, 64), LI_ROW(true, 64)};
-#undef LI_ROW
-LiKernel li_kernel(bool kx, int depth) {   // pbrt_gpu_li_device: kDepth 0 on an LDS-staged tree, 64 beyond
-    for (const LiRow& r : kLiKernels)
-        if (r.kx == kx && r.depth == depth) return r.fn;
-    return nullptr;
-}
-
-using DirectLiKernel = decltype(&k_li_direct<false, 0>);
-struct DirectLiRow { bool kx; int depth; DirectLiKernel fn; const char* name; };
-#define DIRECT_LI_ROW(kx, depth) {kx, depth, &k_li_direct<kx, depth>, "k_li_direct<" #kx ", " #depth ">"}
-const DirectLiRow kDirectLiKernels[] = {DIRECT_LI_ROW(false, 0), DIRECT_LI_ROW(true, 0), DIRECT_LI_ROW(false, 64),
-                                        DIRECT_LI_ROW(true, 64)};
-#undef DIRECT_LI_ROW
-DirectLiKernel direct_li_kernel(bool kx, int depth) {   // pbrt_gpu_direct_li_device: chosen as li_kernel chooses
-    for (const DirectLiRow& r : kDirectLiKernels)
-        if (r.kx == kx && r.depth == depth) return r.fn;
-    return nullptr;
-}
-
-using PathStepKernel = decltype(&k_path_step<false, 0>);
-struct PathStepRow { bool kx; int depth; PathStepKernel fn; const char* name; };
-#define PATH_STEP_ROW(kx, depth) {kx, depth, &k_path_step<kx, depth>, "k_path_step<" #kx ", " #depth ">"}
-const PathStepRow kPathStepKernels[] = {PATH_STEP_ROW(false, 0), PATH_STEP_ROW(true, 0), PATH_STEP_ROW(false, 64),
-                                        PATH_STEP_ROW(true, 64)};
-#undef PATH_STEP_ROW
-PathStepKernel path_step_kernel(bool kx, int depth) {   // pbrt_gpu_path_step_device: chosen as li_kernel chooses
-    for (const PathStepRow& r : kPathStepKernels)
-        if (r.kx == kx && r.depth == depth) return r.fn;
-    return nullptr;
-}
-
-using SerialKernel = decltype(&k_render_exact<1>);
-SerialKernel serial_kernel(int min_waves) {   // the amdgpu_waves_per_eu builds of k_render_exact
-    switch (min_waves) {
-    case 1: return k_render_exact<1>;
-    case 2: return k_render_exact<2>;
-    case 4: return k_render_exact<4>;
-    case 8: return k_render_exact<8>;
-    default: return nullptr;
-    }
 }
 
 // Waves per tile of k_chain_ci for a launch of nb tiles. The frame's EXACT
@@ -1807,424 +1457,6 @@ int pbrt_gpu_film_download(pbrt_gpu_ctx* c, double* film_xyz) {
     return PBRT_OK;
 }
 
-static int intersect_batch(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, int any, pbrt_hit_soa* hits,
-                           uint8_t* occluded) {
-    if (!c || !rays || (!hits && !occluded)) return PBRT_E_INVALID;
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    std::vector<double> packed(n * 7);
-    for (size_t i = 0; i < n; i++) {
-        double* q = &packed[7 * i];
-        q[0] = rays->ox[i]; q[1] = rays->oy[i]; q[2] = rays->oz[i];
-        q[3] = rays->dx[i]; q[4] = rays->dy[i]; q[5] = rays->dz[i];
-        q[6] = rays->tmax ? rays->tmax[i] : gomath::kInf;
-    }
-    size_t nout = any ? n : 9 * n;
-    DevBuf<double> in_buf, out_buf;
-    if (int rc = in_buf.ensure(c, packed.size())) return rc;
-    if (int rc = out_buf.ensure(c, nout)) return rc;
-    double *d_in = in_buf.get(), *d_o = out_buf.get();
-    std::vector<double> o(nout);
-    hipError_t e = hipMemcpyAsync(d_in, packed.data(), sizeof(double) * packed.size(), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        DevScene sc = dev_scene(c, false);
-        launch_k(c, k_intersect, dim3((unsigned)((n + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
-                           with_slot(sc, 7),
-                           (int64_t)n, d_in, d_o, any);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(o.data(), d_o, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) return set_err(c, PBRT_E_HIP, hipGetErrorString(e));
-    int rc = PBRT_OK;
-    for (size_t i = 0; i < n; i++) {
-        if (any) {
-            if (gomath::is_nan(o[i])) rc = PBRT_E_REF_PANIC;
-            occluded[i] = o[i] == 1.0;
-        } else {
-            const double* r = &o[9 * i];
-            if (gomath::is_nan(r[0])) { rc = PBRT_E_REF_PANIC; hits->hit[i] = 0; continue; }
-            hits->hit[i] = r[0] == 1.0;
-            if (hits->t_max) hits->t_max[i] = r[1];
-            if (hits->prim) hits->prim[i] = (int32_t)r[2];
-            if (hits->px) hits->px[i] = r[3];
-            if (hits->py) hits->py[i] = r[4];
-            if (hits->pz) hits->pz[i] = r[5];
-            if (hits->nx) hits->nx[i] = r[6];
-            if (hits->ny) hits->ny[i] = r[7];
-            if (hits->nz) hits->nz[i] = r[8];
-        }
-    }
-    if (rc != PBRT_OK) set_err(c, rc, "the Go reference panics on at least one ray");
-    return rc;
-}
-
-int pbrt_gpu_intersect(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, pbrt_hit_soa* hits) {
-    return intersect_batch(c, rays, n, 0, hits, nullptr);
-}
-int pbrt_gpu_intersect_p(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, uint8_t* occluded) {
-    return intersect_batch(c, rays, n, 1, nullptr, occluded);
-}
-
-// ------------------------------------------------ device-resident queries
-// A query may go on the stream only between frames: a frame in flight owns the
-// context's counters and buffers, and its kernels may be waiting on one another
-// across the context's streams.
-static bool query_blocked(pbrt_gpu_ctx* c) {
-    std::lock_guard<std::mutex> lk(c->cancel.mu);
-    return c->cancel.in_flight;
-}
-// the record cleared, in stream order (so after the queries already enqueued)
-static hipError_t query_rec_clear(pbrt_gpu_ctx* c) {
-    hipError_t e = hipMemsetAsync(&c->d_qrec.get()->panics, 0, sizeof(c->d_qrec.get()->panics), c->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(&c->d_qrec.get()->first, 0xFF, sizeof(c->d_qrec.get()->first), c->stream);
-    return e;
-}
-// the one allocation of the query path, on a context's first query
-static int query_rec_ensure(pbrt_gpu_ctx* c) {
-    if (c->d_qrec.get()) return PBRT_OK;
-    if (int rc = c->d_qrec.ensure(c, 1)) return rc;
-    HIPCHK(c, query_rec_clear(c));
-    return PBRT_OK;
-}
-
-// staged: the diagnostic k_query_hit_staged (pbrt_diag.h), for trees the render kernels stage in LDS
-static int query_hit(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, bool any, const pbrt_hit_soa& hits,
-                     bool staged = false) {
-    if (!c || !rays || !hits.hit) return PBRT_E_INVALID;
-    if (staged && (c->host_scene.n_nodes > kLdsNodes || c->host_scene.n_meshes > 0))
-        return set_err(c, PBRT_E_INVALID, "the staged query takes trees of at most 64 nodes and no mesh");
-    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz)
-        return set_err(c, PBRT_E_INVALID, "a ray array is NULL");
-    if (n > (size_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
-    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = query_rec_ensure(c)) return rc;
-    const DevScene sc = with_slot(dev_scene(c, false), 7);
-    const dim3 grid((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), block(kQueryBlock);
-    const bool mesh_only = c->host_scene.n_prims == 0;   // as the render path chooses its kMeshOnly kernels
-#define PBRT_QUERY_LAUNCH(A, M) \
-    launch_k(c, (k_query_hit<A, M>), grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get())
-    if (staged) {
-        if (any) launch_k(c, k_query_hit_staged<true>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get());
-        else launch_k(c, k_query_hit_staged<false>, grid, block, 0, c->stream, sc, (int64_t)n, *rays, hits, c->d_qrec.get());
-    } else if (any) {
-        if (mesh_only) PBRT_QUERY_LAUNCH(true, true);
-        else PBRT_QUERY_LAUNCH(true, false);
-    } else {
-        if (mesh_only) PBRT_QUERY_LAUNCH(false, true);
-        else PBRT_QUERY_LAUNCH(false, false);
-    }
-#undef PBRT_QUERY_LAUNCH
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-int pbrt_gpu_intersect_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, const pbrt_hit_soa* hits) {
-    if (!hits) return PBRT_E_INVALID;
-    return query_hit(c, rays, n, false, *hits);
-}
-int pbrt_gpu_intersect_p_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, uint8_t* occluded) {
-    pbrt_hit_soa h{};
-    h.hit = occluded;
-    return query_hit(c, rays, n, true, h);
-}
-
-// pbrt_diag.h: the same queries through the LDS-staged walks of the render kernels
-int pbrt_diag_intersect_staged_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, const pbrt_hit_soa* hits) {
-    if (!hits) return PBRT_E_INVALID;
-    return query_hit(c, rays, n, false, *hits, true);
-}
-int pbrt_diag_intersect_p_staged_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, size_t n, uint8_t* occluded) {
-    pbrt_hit_soa h{};
-    h.hit = occluded;
-    return query_hit(c, rays, n, true, h, true);
-}
-int pbrt_gpu_cull_groups(pbrt_gpu_ctx* c) { return c ? c->n_groups : -PBRT_E_INVALID; }
-
-int pbrt_gpu_camera_rays_device(pbrt_gpu_ctx* c, const pbrt_camera_rays_desc* d, const pbrt_ray_soa_out* rays) {
-    if (!c || !d || !rays) return PBRT_E_INVALID;
-    if (!rays->ox || !rays->oy || !rays->oz || !rays->dx || !rays->dy || !rays->dz)
-        return set_err(c, PBRT_E_INVALID, "a ray array is NULL");
-    const pbrt_film_desc& f = c->host_scene.film;
-    if (d->x0 < 0 || d->x0 >= d->x1 || d->x1 > f.res_x || d->y0 < 0 || d->y0 >= d->y1 || d->y1 > f.res_y)
-        return set_err(c, PBRT_E_INVALID, "pixel window outside the film resolution");
-    const int64_t n = (d->x1 - d->x0) * (d->y1 - d->y0);
-    if (n > (int64_t)INT32_MAX) return set_err(c, PBRT_E_INVALID, "more than 2^31 - 1 rays in one query");
-    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_k(c, k_query_camera, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0,
-                       c->stream, c->d_camera.get(), *d, *rays);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-// The light distribution of a Li query's strategy in the query's own buffer (li_device, path_step_device):
-// built, checked and uploaded when the strategy differs from the one last uploaded. n == 0 uploads nothing.
-static int li_distribution(pbrt_gpu_ctx* c, const pbrt_li_desc* d, size_t n) {
-    const char* why = "";
-    if (c->li.strategy == d->light_strategy) return PBRT_OK;
-    // (a refused strategy leaves the uploaded one in place)
-    pbrt_distribution_desc dist;
-    if (int rc = pbrt_scene_light_distribution(&c->host_scene, d->light_strategy, &dist))
-        return set_err(c, rc, "unsupported light sample strategy");
-    if (int rc = pbrtli::check_distribution(c->host_scene.n_lights, dist.func, dist.count, dist.func_int, &why))
-        return set_err(c, rc, why);
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = c->li.d_dist.ensure(c, 1)) return rc;
-    c->li.host_dist = dist;
-    c->li.strategy = 0;
-    HIPCHK(c, hipMemcpyAsync(c->li.d_dist.get(), &c->li.host_dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
-    c->li.strategy = d->light_strategy;
-    return PBRT_OK;
-}
-
-// Integrator.Li over device arrays (k_li.hip). The checks and the kernel choice: li_query.h.
-int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng,
-                       size_t n, const pbrt_radiance_soa* out) {
-    const char* why = "";
-    if (int rc = pbrtli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
-        return set_err(c, rc, why);
-    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
-    if (int rc = li_distribution(c, d, n)) return rc;
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = query_rec_ensure(c)) return rc;
-    DevScene sc = with_slot(dev_scene(c, false), 7);
-    sc.dist = c->li.d_dist.get();
-    const pbrtli::KernelArgs ka =
-        pbrtli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
-    const LiKernel kern = li_kernel(ka.kx, ka.depth);
-    if (!kern) return set_err(c, PBRT_E_HIP, "no k_li instantiation for depth " + std::to_string(ka.depth));
-    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
-             *rays, *rng, *out, c->d_qrec.get());
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-// Path.Li one iteration at a time over device path state (k_path_step.hip). The checks, the queue rules and the
-// grids: path_query.h; the desc's refusals, the distribution and the instantiation's choice are the li query's.
-int pbrt_gpu_path_begin_device(pbrt_gpu_ctx* c, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng, size_t n,
-                               const pbrt_path_soa* paths) {
-    const char* why = "";
-    if (int rc = pbrtpath::check_begin(c != nullptr, rays, rng, n, paths, c && query_blocked(c), &why))
-        return set_err(c, rc, why);
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    launch_k(c, k_path_begin, dim3(pbrtpath::begin_grid(n)), dim3(pbrtpath::kBeginBlock), 0, c->stream, (int64_t)n, *rays,
-             *rng, *paths);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-int pbrt_gpu_path_step_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_path_soa* paths, const pbrt_path_queue* in,
-                              const pbrt_path_queue* out, size_t n, const pbrt_path_step_soa* step) {
-    const char* why = "";
-    if (int rc = pbrtpath::check_step(c != nullptr, d, paths, in, out, n, c && query_blocked(c), &why))
-        return set_err(c, rc, why);
-    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
-    if (int rc = li_distribution(c, d, n)) return rc;
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = query_rec_ensure(c)) return rc;
-    DevScene sc = with_slot(dev_scene(c, false), 7);
-    sc.dist = c->li.d_dist.get();
-    const pbrtli::KernelArgs ka =
-        pbrtpath::step_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
-    const PathStepKernel kern = path_step_kernel(ka.kx, ka.depth);
-    if (!kern) return set_err(c, PBRT_E_HIP, "no k_path_step instantiation for depth " + std::to_string(ka.depth));
-    if (out) HIPCHK(c, hipMemsetAsync(out->count, 0, sizeof(uint32_t), c->stream));
-    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
-             *paths, in ? *in : pbrt_path_queue{nullptr, nullptr}, out ? *out : pbrt_path_queue{nullptr, nullptr},
-             step ? *step : pbrt_path_step_soa{}, c->d_qrec.get());
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-// DirectLighting.Li over device arrays (k_li_direct.hip). The checks, the kernel choice, the capped grid and
-// the size of the level records: direct_li_query.h. No light distribution: one launch a call.
-int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* c, const pbrt_direct_li_desc* d, const pbrt_ray_soa* rays,
-                              const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out) {
-    const char* why = "";
-    if (int rc = pbrtdli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
-        return set_err(c, rc, why);
-    if (int rc = pbrtdli::check_supported(*d, c->rough_glass, c->non_matte, &why)) return set_err(c, rc, why);
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (int rc = query_rec_ensure(c)) return rc;
-    const DevScene sc = with_slot(dev_scene(c, false), 7);
-    const pbrtdli::KernelArgs ka = pbrtdli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n,
-                                                        kLdsNodes, c->knobs.direct_li_grid, d->max_depth);
-    const DirectLiKernel kern = direct_li_kernel(ka.kx, ka.depth);
-    if (!kern) return set_err(c, PBRT_E_HIP, "no k_li_direct instantiation for depth " + std::to_string(ka.depth));
-    if (ka.level_doubles > 0)   // (grows only: a smaller query runs in the buffer of a larger one)
-        if (int rc = c->d_dli_levels.ensure(c, ka.level_doubles)) return rc;
-    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, (int)d->dl_strategy, ka.levels,
-             (int64_t)n, *rays, *rng, *out, c->d_qrec.get(), ka.level_doubles > 0 ? c->d_dli_levels.get() : nullptr);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-// (diagnostics) the capacity of the level-record buffer in bytes: it changes only when the buffer is allocated anew
-size_t pbrt_gpu_direct_li_scratch_bytes(const pbrt_gpu_ctx* c) { return c ? c->d_dli_levels.cap() * sizeof(double) : 0; }
-
-// ---- a frame from public pieces (k_film_q.hip). The layout, the checks and the refusals: film_query.h.
-// The RenderParams the film kernels' tile_bounds / film_tile_bounds read, for a tile size of the caller's.
-static RenderParams frame_params(const pbrt_gpu_ctx* c, const pbrtfilm::Layout& l) {
-    const pbrt_film_desc& f = c->host_scene.film;
-    RenderParams rp{};
-    rp.film_min_x = l.min_x;
-    rp.film_min_y = l.min_y;
-    rp.film_w = l.w;
-    rp.film_h = l.h;
-    rp.tile_size = l.ts;
-    rp.ntx = l.ntx;
-    rp.nty = l.nty;
-    rp.tile_stride = 1;
-    rp.slot_w = pbrtfilm::slot_extent(l.ts, f.filter_radius_x);
-    rp.slot_h = pbrtfilm::slot_extent(l.ts, f.filter_radius_y);
-    return rp;
-}
-
-int64_t pbrt_gpu_frame_count(const pbrt_gpu_ctx* c, const pbrt_frame_desc* d) {
-    const char* why = "";
-    int64_t n = 0;
-    if (pbrtfilm::check_frame(c != nullptr, c ? &c->host_scene.film : nullptr, d, PBRT_FILM_ADD_CLEAR, false, &n, &why))
-        return -PBRT_E_INVALID;
-    return n;
-}
-
-int pbrt_gpu_frame_samples_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, const pbrt_frame_samples_soa* out) {
-    const char* why = "";
-    int64_t n = 0;
-    const pbrt_film_desc* f = c ? &c->host_scene.film : nullptr;
-    if (int rc = pbrtfilm::check_frame(c != nullptr, f, d, 0, c && query_blocked(c), &n, &why)) return set_err(c, rc, why);
-    if (int rc = pbrtfilm::check_samples_out(out, &why)) return set_err(c, rc, why);
-    if (int rc = pbrtfilm::check_frame_supported(*f, *d, false, &why)) return set_err(c, rc, why);
-    if (n == 0) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
-    launch_k(c, k_frame_samples, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0, c->stream,
-             c->d_camera.get(), l, pbrtfilm::pixels_before(l, d->tile_begin), (int)d->ns, n, *out);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-int pbrt_gpu_film_add_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, const pbrt_film_samples_soa* in,
-                             double* film_device) {
-    const char* why = "";
-    int64_t n = 0;
-    const pbrt_film_desc* f = c ? &c->host_scene.film : nullptr;
-    if (int rc = pbrtfilm::check_frame(c != nullptr, f, d, PBRT_FILM_ADD_CLEAR, c && query_blocked(c), &n, &why))
-        return set_err(c, rc, why);
-    if (int rc = pbrtfilm::check_film_in(in, film_device, &why)) return set_err(c, rc, why);
-    if (int rc = pbrtfilm::check_frame_supported(*f, *d, true, &why)) return set_err(c, rc, why);
-    const bool clear = (d->flags & PBRT_FILM_ADD_CLEAR) != 0;
-    if (n == 0 && !clear) return PBRT_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
-    const RenderParams rp = frame_params(c, l);
-    const int64_t nt = d->tile_end - d->tile_begin;
-    if (nt > 0) {
-        if (int rc = c->d_fq_films.ensure(c, pbrtfilm::scratch_doubles(*f, d->tile_size, d->tile_begin, d->tile_end)))
-            return rc;
-        launch_k(c, pbrtfilm::lds_gather(c->knobs.film_add_lds, *f, d->tile_size) ? k_film_add_tiles<true> : k_film_add_tiles<false>,
-                 dim3((unsigned)nt), dim3(kFilmThreads), 0, c->stream, c->d_film.get(), rp, l, (int64_t)d->tile_begin,
-                 (int)d->ns, *in, c->d_fq_films.get());
-    }
-    const pbrtfilm::Rows rows = pbrtfilm::rows_touched(l, *f, d->tile_begin, d->tile_end, clear);
-    const int64_t npx = (rows.y1 - rows.y0) * l.w;
-    if (npx > 0)
-        launch_k(c, k_film_add_merge, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, c->stream, c->d_film.get(), rp,
-                 (int64_t)d->tile_begin, (int64_t)d->tile_end, rows.y0, rows.y1 - rows.y0, clear ? 1 : 0,
-                 (const double*)c->d_fq_films.get(), film_device);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-int pbrt_gpu_film_rgba8_device(pbrt_gpu_ctx* c, const double* film_device, int64_t w, int64_t h, uint8_t* rgba_device) {
-    const char* why = "";
-    if (int rc = pbrtfilm::check_rgba8(c != nullptr, film_device, w, h, rgba_device, c && query_blocked(c), &why))
-        return set_err(c, rc, why);
-    HIPCHK(c, hipSetDevice(c->device));
-    const int64_t n = w * h;
-    launch_k(c, k_film_rgba8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, film_device, n,
-             (uint32_t*)rgba_device);
-    HIPCHK(c, hipGetLastError());
-    return PBRT_OK;
-}
-
-// (diagnostics) the capacity of film_add's scratch buffer in bytes: it changes only when the buffer is allocated anew
-size_t pbrt_gpu_film_scratch_bytes(const pbrt_gpu_ctx* c) { return c ? c->d_fq_films.cap() * sizeof(double) : 0; }
-
-int pbrt_gpu_query_status(pbrt_gpu_ctx* c, pbrt_query_record* out) {
-    if (!c) return PBRT_E_INVALID;
-    if (query_blocked(c)) return set_err(c, PBRT_E_INVALID, "a render is in flight on this context");
-    HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    QueryRec rec{0, ~0ull};
-    if (c->d_qrec.get()) {
-        HIPCHK(c, hipMemcpy(&rec, c->d_qrec.get(), sizeof(rec), hipMemcpyDeviceToHost));
-        if (rec.panics) HIPCHK(c, query_rec_clear(c));
-    }
-    if (out) {
-        out->panics = rec.panics;
-        out->first_ray = rec.panics ? (int64_t)(rec.first >> 8) : -1;
-        out->panic_kind = rec.panics ? (int32_t)(rec.first & 0xFF) : PBRT_PANIC_NONE;
-        out->pad0 = 0;
-    }
-    if (rec.panics) return set_err(c, PBRT_E_REF_PANIC, "the Go reference panics on at least one ray");
-    return PBRT_OK;
-}
-
-// ---- buffers the context owns (bookkeeping: query_buffers.h)
-int pbrt_gpu_buffer_create(pbrt_gpu_ctx* c, size_t bytes, pbrt_gpu_buffer** out) {
-    if (out) *out = nullptr;
-    if (!c || !out || bytes == 0) return PBRT_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    hipError_t e = hipSuccess;
-    pbrt_gpu_buffer* b = pbrtq::list_create(c->qbufs, c, bytes, [&e](size_t nb) {
-        void* p = nullptr;
-        e = hipMalloc(&p, nb);
-        return e == hipSuccess ? p : nullptr;
-    });
-    if (!b) return set_err(c, PBRT_E_HIP, std::string("hipMalloc: ") + hipGetErrorString(e));
-    *out = b;
-    return PBRT_OK;
-}
-void* pbrt_gpu_buffer_ptr(const pbrt_gpu_buffer* b) { return b ? b->ptr : nullptr; }
-size_t pbrt_gpu_buffer_size(const pbrt_gpu_buffer* b) { return b ? b->bytes : 0; }
-
-static int buffer_copy(pbrt_gpu_buffer* b, size_t offset, void* host, size_t bytes, bool up) {
-    if (!b || !b->ctx) return PBRT_E_INVALID;
-    pbrt_gpu_ctx* c = b->ctx;
-    if (!host && bytes) return set_err(c, PBRT_E_INVALID, "NULL host pointer");
-    if (!pbrtq::range_ok(b->bytes, offset, bytes)) return set_err(c, PBRT_E_INVALID, "range outside the buffer");
-    HIPCHK(c, hipSetDevice(c->device));
-    char* dev = (char*)b->ptr + offset;
-    if (bytes) {
-        if (up) HIPCHK(c, hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, c->stream));
-        else HIPCHK(c, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return PBRT_OK;
-}
-int pbrt_gpu_buffer_upload(pbrt_gpu_buffer* b, size_t offset, const void* host, size_t bytes) {
-    return buffer_copy(b, offset, const_cast<void*>(host), bytes, true);
-}
-int pbrt_gpu_buffer_download(pbrt_gpu_buffer* b, size_t offset, void* host, size_t bytes) {
-    return buffer_copy(b, offset, host, bytes, false);
-}
-void pbrt_gpu_buffer_destroy(pbrt_gpu_buffer* b) {
-    if (!b || !b->ctx) return;
-    pbrt_gpu_ctx* c = b->ctx;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);   // no query still reads or writes it
-    pbrtq::list_destroy(c->qbufs, b, [](void* p) { (void)hipFree(p); });
-}
-
 void pbrt_gpu_cancel(pbrt_gpu_ctx* c) {
     if (!c) return;
     std::lock_guard<std::mutex> lk(c->cancel.mu);
@@ -2284,387 +1516,3 @@ int pbrt_film_to_rgba8(const double* film, int64_t w, int64_t h, uint8_t* rgba) 
 }
 
 }  // extern "C"
-
-// ============================================================ diagnostics
-
-namespace {
-__global__ void k_probe(int op, const double* __restrict__ in, int64_t n, int in_stride, double* __restrict__ out,
-                        int out_stride) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const double* a = in + i * in_stride;
-    double* o = out + i * out_stride;
-    switch (op) {
-        case PBRT_PROBE_SIN: o[0] = gomath::sin(a[0]); break;
-        case PBRT_PROBE_COS: o[0] = gomath::cos(a[0]); break;
-        case PBRT_PROBE_TAN: o[0] = gomath::tan(a[0]); break;
-        case PBRT_PROBE_ATAN: o[0] = gomath::atan(a[0]); break;
-        case PBRT_PROBE_ATAN2: o[0] = gomath::atan2(a[0], a[1]); break;
-        case PBRT_PROBE_ASIN: o[0] = gomath::asin(a[0]); break;
-        case PBRT_PROBE_ACOS: o[0] = gomath::acos(a[0]); break;
-        case PBRT_PROBE_SQRT: o[0] = gomath::sqrt(a[0]); break;
-        case PBRT_PROBE_DIV: o[0] = a[0] / a[1]; break;
-        case PBRT_PROBE_NEXTAFTER: o[0] = gomath::nextafter(a[0], a[1]); break;
-        case PBRT_PROBE_MAX: o[0] = gomath::max(a[0], a[1]); break;
-        case PBRT_PROBE_MIN: o[0] = gomath::min(a[0], a[1]); break;
-        case PBRT_PROBE_OFFSET_RAY_ORIGIN: {
-            V3 r = offset_ray_origin(load3(a), load3(a + 3), load3(a + 6), load3(a + 9));
-            o[0] = r.x; o[1] = r.y; o[2] = r.z;
-            break;
-        }
-        case PBRT_PROBE_EFLOAT_ADD: {
-            int panic = 0;
-            EF r = ef_add(ef_new(a[0], a[1], panic), ef_new(a[2], a[3], panic), panic);
-            o[0] = r.v; o[1] = r.lo; o[2] = r.hi; o[3] = panic;
-            break;
-        }
-        case PBRT_PROBE_TRANSFORM_RAY: {
-            pbrt_matrix4x4 m;
-            for (int k = 0; k < 16; k++) m.m[k / 4][k % 4] = a[k];
-            Ray r{load3(a + 16), load3(a + 19), gomath::kInf, 0};
-            Ray w = xf_ray(m, r, nullptr, nullptr);
-            o[0] = w.o.x; o[1] = w.o.y; o[2] = w.o.z; o[3] = w.d.x; o[4] = w.d.y; o[5] = w.d.z;
-            break;
-        }
-        case PBRT_PROBE_SPAWN_RAY_TO: {
-            V3 p0 = load3(a), e0 = load3(a + 3), n0 = load3(a + 6), p1 = load3(a + 9), e1 = load3(a + 12),
-               n1 = load3(a + 15);
-            V3 origin = offset_ray_origin(p0, e0, n0, p1 - p0);
-            V3 target = offset_ray_origin(p1, e1, n1, origin - p1);
-            V3 d = target - origin;
-            o[0] = p0.x; o[1] = p0.y; o[2] = p0.z; o[3] = d.x; o[4] = d.y; o[5] = d.z; o[6] = 1 - 0.0001;
-            break;
-        }
-        case PBRT_PROBE_PCG: {
-            Pcg r;
-            pcg_seed(r, (uint64_t)a[0]);
-            for (int k = 0; k < out_stride; k++) o[k] = pcg_float(r);
-            break;
-        }
-        case PBRT_PROBE_MIN_NONAN: o[0] = gomath::min_nonan(a[0], a[1]); break;
-        case PBRT_PROBE_MAX_NONAN: o[0] = gomath::max_nonan(a[0], a[1]); break;
-        case PBRT_PROBE_EFLOAT_MUL:
-        case PBRT_PROBE_EFLOAT_DIV: {
-            int panic = 0;
-            EF x = ef_new(a[0], a[1], panic), y = ef_new(a[2], a[3], panic);
-            EF r = op == PBRT_PROBE_EFLOAT_MUL ? ef_mul(x, y, panic) : ef_div(x, y, panic);
-            o[0] = r.v; o[1] = r.lo; o[2] = r.hi; o[3] = panic;
-            break;
-        }
-        case PBRT_PROBE_NEXT_FLOAT_UP: o[0] = gomath::next_up(a[0]); break;
-        case PBRT_PROBE_NEXT_FLOAT_DOWN: o[0] = gomath::next_down(a[0]); break;
-        case PBRT_PROBE_SINCOS: {
-            double s, c;
-            gomath::sincos(a[0], s, c);
-            o[0] = s; o[1] = c;
-            break;
-        }
-        case PBRT_PROBE_CONCENTRIC_DISK: {
-            V2 d = concentric_sample_disk(V2{a[0], a[1]});
-            o[0] = d.x; o[1] = d.y;
-            break;
-        }
-        default: o[0] = gomath::nan();
-    }
-}
-}  // namespace
-
-extern "C" int pbrt_gpu_probe(int device, int op, const double* in, size_t n, int in_stride, double* out,
-                              int out_stride) {
-    if (!in || !out || in_stride <= 0 || out_stride <= 0) return PBRT_E_INVALID;
-    if ((op == PBRT_PROBE_SINCOS || op == PBRT_PROBE_CONCENTRIC_DISK) && out_stride < 2) return PBRT_E_INVALID;
-    if (op == PBRT_PROBE_CONCENTRIC_DISK && in_stride < 2) return PBRT_E_INVALID;
-    if (n == 0) return PBRT_OK;
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) return PBRT_E_HIP;
-    DevBuf<double> in_buf, out_buf;
-    if (in_buf.ensure(nullptr, n * in_stride) != PBRT_OK || out_buf.ensure(nullptr, n * out_stride) != PBRT_OK)
-        return PBRT_E_HIP;
-    double *d_in = in_buf.get(), *d_out = out_buf.get();
-    hipError_t e = hipMemcpy(d_in, in, sizeof(double) * n * in_stride, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        launch_logged(nullptr, 0, k_probe, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, op, d_in, (int64_t)n,
-                           in_stride, d_out, out_stride);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * n * out_stride, hipMemcpyDeviceToHost);
-    return e == hipSuccess ? PBRT_OK : PBRT_E_HIP;
-}
-
-extern "C" int pbrt_gpu_counters(pbrt_gpu_ctx* c, uint64_t* out, int n) {
-    if (!c || !out) return PBRT_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) return PBRT_E_HIP;
-    Counters ctr;
-    if (hipMemcpy(&ctr, c->d_ctr.get(), sizeof(ctr), hipMemcpyDeviceToHost) != hipSuccess) return PBRT_E_HIP;
-    const uint64_t v[kNumCounters] = {ctr.paths,    ctr.camera_samples, ctr.closest_rays, ctr.shadow_rays,
-                                      (uint64_t)ctr.any_panic, ctr.windows, ctr.phase[0], ctr.phase[1],
-                                      ctr.phase[2], ctr.phase[3], ctr.phase[4], ctr.phase[5],
-                                      ctr.phase[6], ctr.phase[7]};
-    for (int i = 0; i < n && i < kNumCounters; i++)
-        out[i] = i < 14 ? v[i] : i < 78 ? (uint64_t)ctr.dhist[i - 14] : i == 78 ? ctr.busy : i == 79 ? ctr.nps_issued
-                                                                                                   : ctr.odd_d;
-    return kNumCounters;
-}
-
-extern "C" int pbrt_gpu_mesh_info(pbrt_gpu_ctx* c, double* out, int n) {
-    if (!c || !out) return -PBRT_E_INVALID;
-    const double v[] = {(double)c->mesh.n_tris, (double)c->mesh.n_nodes, (double)c->mesh.depth, c->mesh.build_ms,
-                        (double)c->mesh.n_meshes, (double)PBRT_MESH_WIDE};
-    const int m = (int)(sizeof(v) / sizeof(v[0]));
-    for (int i = 0; i < n && i < m; i++) out[i] = v[i];
-    return m;
-}
-extern "C" int pbrt_gpu_mesh_counters(uint64_t* out, int n, int reset) {
-#ifdef PBRT_MESH_COUNT
-    unsigned long long h[kMeshCountSlots * 6];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_mesh_count), sizeof(h)) != hipSuccess) return -PBRT_E_HIP;
-    for (int i = 0; i < n && i < kMeshCountSlots * 6; i++) out[i] = h[i];
-    if (reset) {
-        std::memset(h, 0, sizeof(h));
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_mesh_count), h, sizeof(h)) != hipSuccess) return -PBRT_E_HIP;
-    }
-    return kMeshCountSlots * 6;
-#else
-    (void)out; (void)n; (void)reset;
-    return 0;
-#endif
-}
-
-extern "C" int pbrt_gpu_mesh_download(pbrt_gpu_ctx* c, void* nodes, int32_t* gid, float* tris) {
-    if (!c) return PBRT_E_INVALID;
-    if (hipSetDevice(c->device) != hipSuccess) return PBRT_E_HIP;
-    const size_t nn = mesh_node_bytes(c->mesh.n_nodes), nt = (size_t)c->mesh.n_tris;
-    if (nodes && nn && hipMemcpy(nodes, c->mesh.nodes, nn, hipMemcpyDeviceToHost) != hipSuccess)
-        return PBRT_E_HIP;
-    if (gid && nt && hipMemcpy(gid, c->mesh.gid, nt * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        return PBRT_E_HIP;
-    if (tris && nt && hipMemcpy(tris, c->mesh.tris, nt * 9 * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
-        return PBRT_E_HIP;
-    return PBRT_OK;
-}
-
-extern "C" int64_t pbrt_gpu_tile_clocks(pbrt_gpu_ctx* c, uint32_t* start, uint32_t* end, int64_t n) {
-    if (!c) return -PBRT_E_INVALID;
-    const int64_t m = (int64_t)c->sched.h_tick_clocks.size() / 2;
-    for (int64_t i = 0; i < m && i < n; i++) {
-        if (start) start[i] = c->sched.h_tick_clocks[(size_t)i];
-        if (end) end[i] = c->sched.h_tick_clocks[(size_t)(m + i)];
-    }
-    return m;
-}
-
-extern "C" int64_t pbrt_gpu_tile_ticks(pbrt_gpu_ctx* c, uint32_t* out, int64_t n, int64_t* heavy) {
-    if (!c) return -PBRT_E_INVALID;
-    if (heavy) *heavy = c->sched.last_heavy;
-    const int64_t m = (int64_t)c->sched.h_last_ticks.size();
-    for (int64_t i = 0; out && i < n && i < m; i++) out[i] = c->sched.h_last_ticks[(size_t)i];
-    return m;
-}
-
-extern "C" void pbrt_gpu_schedule_cache_clear(void) {
-    sched_cache_clear();
-}
-
-extern "C" int64_t pbrt_gpu_overlap_slots(pbrt_gpu_ctx* c) {
-    if (!c) return -PBRT_E_INVALID;
-    return c->ov.done;
-}
-
-// ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
-// kernel the library compiles, spelled as its explicit instantiation is
-// (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
-// k_paths_ci, k_paths_cam[_stack], k_li, k_li_direct and k_path_step families are named by their selectors' tables.
-namespace {
-const KernelName kKernelNames[] = {
-    // k_paths_m.hip, k_paths_x.hip
-    PBRT_KERNEL_NAME(k_mb_setup<false>),
-    PBRT_KERNEL_NAME(k_mb_setup<true>),
-    // k_chain_c.hip, k_paths_c.hip
-    PBRT_KERNEL_NAME(k_chain_cam),
-    PBRT_KERNEL_NAME(k_cam_setup),
-    PBRT_KERNEL_NAME(k_chain_cam_stack),
-    PBRT_KERNEL_NAME(k_film_cam<false>),
-    PBRT_KERNEL_NAME(k_film_cam<true>),
-    // k_serial.hip
-    PBRT_KERNEL_NAME(k_render_exact<1>),
-    PBRT_KERNEL_NAME(k_render_exact<2>),
-    PBRT_KERNEL_NAME(k_render_exact<4>),
-    PBRT_KERNEL_NAME(k_render_exact<8>),
-    // k_pw.hip
-    PBRT_KERNEL_NAME(k_pw_trace<false>),
-    PBRT_KERNEL_NAME(k_pw_trace<true>),
-    PBRT_KERNEL_NAME(k_pw_shadow<false>),
-    PBRT_KERNEL_NAME(k_pw_shadow<true>),
-    PBRT_KERNEL_NAME(k_pw_cache<false>),
-    PBRT_KERNEL_NAME(k_pw_cache<true>),
-    PBRT_KERNEL_NAME(k_pw_start<false, false>),
-    PBRT_KERNEL_NAME(k_pw_start<false, true>),
-    PBRT_KERNEL_NAME(k_pw_start<true, false>),
-    PBRT_KERNEL_NAME(k_pw_start<true, true>),
-    PBRT_KERNEL_NAME(k_pw_shade<false>),
-    PBRT_KERNEL_NAME(k_pw_shade<true>),
-    PBRT_KERNEL_NAME(k_pw_scan),
-    PBRT_KERNEL_NAME(k_pw_scatter),
-    PBRT_KERNEL_NAME(k_pw_panics),
-    // k_frame.hip
-    PBRT_KERNEL_NAME(k_film),
-    PBRT_KERNEL_NAME(k_panic_reduce),
-    PBRT_KERNEL_NAME(k_wf_primary<false>),
-    PBRT_KERNEL_NAME(k_wf_primary<true>),
-    PBRT_KERNEL_NAME(k_dl_setup),
-    PBRT_KERNEL_NAME(k_dl_samples<false>),
-    PBRT_KERNEL_NAME(k_dl_samples<true>),
-    PBRT_KERNEL_NAME(k_dl_panics),
-    PBRT_KERNEL_NAME(k_tile_cost<false>),
-    PBRT_KERNEL_NAME(k_tile_cost<true>),
-    PBRT_KERNEL_NAME(k_gate),
-    PBRT_KERNEL_NAME(k_order_of_keys),
-    PBRT_KERNEL_NAME(k_merge_film),
-    PBRT_KERNEL_NAME(k_intersect),
-    // k_group.hip, k_query.hip, this unit
-    PBRT_KERNEL_NAME(k_merge_film_group),
-    PBRT_KERNEL_NAME(k_query_hit<false, false>),
-    PBRT_KERNEL_NAME(k_query_hit<true, false>),
-    PBRT_KERNEL_NAME(k_query_hit<false, true>),
-    PBRT_KERNEL_NAME(k_query_hit<true, true>),
-    PBRT_KERNEL_NAME(k_query_hit_staged<false>),
-    PBRT_KERNEL_NAME(k_query_hit_staged<true>),
-    PBRT_KERNEL_NAME(k_query_camera),
-    PBRT_KERNEL_NAME(k_probe),
-    // k_film_q.hip
-    PBRT_KERNEL_NAME(k_frame_samples),
-    PBRT_KERNEL_NAME(k_film_add_tiles<false>),
-    PBRT_KERNEL_NAME(k_film_add_tiles<true>),
-    PBRT_KERNEL_NAME(k_film_add_merge),
-    PBRT_KERNEL_NAME(k_film_rgba8),
-    // k_path_step.hip
-    PBRT_KERNEL_NAME(k_path_begin),
-};
-
-template <class F>
-void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' tables, kKernelNames, the LBVH unit's
-    for (const ChainRow& r : kChainKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const PathsCiRow& r : kPathsCiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const LiRow& r : kLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const DirectLiRow& r : kDirectLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const PathStepRow& r : kPathStepKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
-    for (const KernelName& k : kKernelNames) f(k.fn, k.name);
-    size_t nm = 0;
-    const KernelName* mk = mesh_bvh_kernel_names(&nm);
-    for (size_t i = 0; i < nm; i++) f(mk[i].fn, mk[i].name);
-}
-const char* kernel_name_of(const void* fn, const char* unknown = "?") {
-    const char* name = unknown;
-    each_kernel([&](const void* f, const char* n) { if (f == fn) name = n; });
-    return name;
-}
-}  // namespace
-
-extern "C" int pbrt_gpu_kernel_names(const char** out, int n) {
-    int k = 0;
-    each_kernel([&](const void*, const char* name) {
-        if (out && k < n) out[k] = name;
-        k++;
-    });
-    return k;
-}
-
-extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a, int n) {
-    if (!family || !a) return nullptr;
-    const std::string f = family;
-    const void* fn = nullptr;
-    if (f == "k_chain_ci" && n == 6)
-        fn = reinterpret_cast<const void*>(chain_kernel(a[0], a[1], a[2] != 0, a[3], a[4] != 0, a[5] != 0));
-    else if (f == "k_paths_ci" && n == 3)
-        fn = reinterpret_cast<const void*>(paths_ci_kernel(a[0], a[1] != 0, a[2] != 0));
-    else if (f == "k_paths_cam" && n == 3)
-        fn = reinterpret_cast<const void*>(paths_cam_kernel(a[0], a[1] != 0, a[2] != 0));
-    else if (f == "k_render_exact" && n == 1)
-        fn = reinterpret_cast<const void*>(serial_kernel(a[0]));
-    else if (f == "k_li" && n == 2)
-        fn = reinterpret_cast<const void*>(li_kernel(a[0] != 0, a[1]));
-    else if (f == "k_li_direct" && n == 2)
-        fn = reinterpret_cast<const void*>(direct_li_kernel(a[0] != 0, a[1]));
-    else if (f == "k_path_step" && n == 2)
-        fn = reinterpret_cast<const void*>(path_step_kernel(a[0] != 0, a[1]));
-    return fn ? kernel_name_of(fn, nullptr) : nullptr;
-}
-
-extern "C" int64_t pbrt_gpu_launch_log(pbrt_gpu_ctx* c, int which, pbrt_launch_rec* out, int64_t n, uint64_t* overflow) {
-    if (!c || (which != PBRT_LAUNCHES_FRAME && which != PBRT_LAUNCHES_OUTSIDE)) return -PBRT_E_INVALID;
-    const LaunchLog& log = which == PBRT_LAUNCHES_FRAME ? c->log_frame : c->log_aux;
-    if (overflow) *overflow = log.overflow;
-    const int64_t m = (int64_t)log.recs.size();
-    if (out && n > 0 && hipSetDevice(c->device) != hipSuccess) return -PBRT_E_HIP;
-    for (int64_t i = 0; out && i < n && i < m; i++) {
-        const LaunchRec& r = log.recs[(size_t)i];
-        pbrt_launch_rec& o = out[i];
-        o.name = kernel_name_of(r.fn);
-        o.fn = r.fn;
-        for (int k = 0; k < 3; k++) {
-            o.grid[k] = r.grid[k];
-            o.block[k] = r.block[k];
-        }
-        o.lds_dynamic = r.lds;
-        hipFuncAttributes fa;
-        o.lds_static = hipFuncGetAttributes(&fa, r.fn) == hipSuccess ? (uint32_t)fa.sharedSizeBytes : 0xFFFFFFFFu;
-        o.stream = r.stream;
-        o.pad0 = 0;
-    }
-    return m;
-}
-
-extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->dev.lds_per_block : -PBRT_E_INVALID; }
-
-extern "C" int pbrt_gpu_schedule_source(pbrt_gpu_ctx* c) {
-    if (!c) return -PBRT_E_INVALID;
-    return c->sched.src;
-}
-
-extern "C" int64_t pbrt_gpu_tile_costs(pbrt_gpu_ctx* c, float* out, int64_t n) {
-    if (!c) return -PBRT_E_INVALID;
-    if (!c->sched.probed || !c->sched.d_cost.get()) return 0;
-    if (out && n > 0) {
-        const int64_t m = std::min<int64_t>(n, c->sched.cost_n);
-        if (hipSetDevice(c->device) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess ||
-            hipMemcpy(out, c->sched.d_cost.get(), sizeof(float) * 4 * (size_t)m, hipMemcpyDeviceToHost) != hipSuccess)
-            return -PBRT_E_HIP;
-    }
-    return c->sched.cost_n;
-}
-
-// Region cycles of trajectory steps (PBRT_STEP_TIMING builds only; else zeros):
-// [0] loop top / light-sample draws, [1] closest-hit traversal + interaction,
-// [2] BSDF setup, [3] light sampling (full paths), [4] BSDF sample + spawn + RR.
-extern "C" int pbrt_gpu_step_cycles(uint64_t* out, int n, int reset) {
-#ifdef PBRT_STEP_TIMING
-    unsigned long long h[8];
-    if (hipMemcpyFromSymbol(h, HIP_SYMBOL(g_step_cycles), sizeof(h)) != hipSuccess) return PBRT_E_HIP;
-    for (int i = 0; i < n && i < 8; i++) out[i] = h[i];
-    if (reset) {
-        std::memset(h, 0, sizeof(h));
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_step_cycles), h, sizeof(h)) != hipSuccess) return PBRT_E_HIP;
-    }
-#else
-    for (int i = 0; i < n && i < 8; i++) out[i] = 0;
-    (void)reset;
-#endif
-    return 8;
-}
-
-#ifndef PBRT_BUILD_ID
-#define PBRT_BUILD_ID "unknown"
-#endif
-extern "C" const char* pbrt_gpu_build_id(void) { return PBRT_BUILD_ID; }
-
-extern "C" int pbrt_abi_sizes(size_t* out, int n) {
-    const size_t s[] = {sizeof(pbrt_matrix4x4),   sizeof(pbrt_transform),    sizeof(pbrt_shape_desc),
-                        sizeof(pbrt_material_desc), sizeof(pbrt_primitive_desc), sizeof(pbrt_bvh_node),
-                        sizeof(pbrt_light_desc),  sizeof(pbrt_camera_desc),  sizeof(pbrt_film_desc),
-                        sizeof(pbrt_distribution_desc), sizeof(pbrt_scene_desc), sizeof(pbrt_render_desc),
-                        sizeof(pbrt_gpu_stats),   sizeof(pbrt_ray_soa),      sizeof(pbrt_hit_soa),
-                        sizeof(pbrt_gpu_opts),    sizeof(pbrt_mesh_desc)};
-    int m = (int)(sizeof(s) / sizeof(s[0]));
-    for (int i = 0; i < n && i < m; i++) out[i] = s[i];
-    return m;
-}

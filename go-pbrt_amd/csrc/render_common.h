@@ -1,6 +1,6 @@
 // render_common.h — types and device helpers shared by the kernel translation
-// units (k_*.hip) and the host code of render.hip. Namespace pbrtk: the kernels
-// are defined in their own translation units and launched from render.hip
+// units (k_*.hip) and the host units (render.hip's map). Namespace pbrtk: the kernels
+// are defined in their own translation units and launched from the host units
 // through the declarations of render_kernels.h.
 
 #pragma once
@@ -69,6 +69,11 @@ struct QueryRec {
     unsigned long long panics;   // rays on which the reference panics (atomicAdd)
     unsigned long long first;    // smallest (ray index << 8 | PBRT_PANIC_*) of them (atomicMin); ~0: none
 };
+// ray i of a query, on which the reference panics with `kind`, into the record
+__device__ __forceinline__ void query_panic(QueryRec* __restrict__ rec, int64_t i, int kind) {
+    atomicAdd(&rec->panics, 1ull);
+    atomicMin(&rec->first, ((unsigned long long)i << 8) | (unsigned long long)(kind & 0xFF));
+}
 
 __device__ __forceinline__ void tile_bounds(const RenderParams& rp, int64_t tile, int64_t& x0, int64_t& y0,
                                             int64_t& x1, int64_t& y1) {

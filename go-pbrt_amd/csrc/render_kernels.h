@@ -1,6 +1,7 @@
-// render_kernels.h — declarations of the kernels, for the host code of render.hip.
-// Each kernel is defined (and its template instantiations made) in its own
-// translation unit; the launch goes through the host stub that unit emits.
+// render_kernels.h — declarations of the kernels, for the host units (render.hip,
+// queries.hip, kernel_select.hip, group.hip). Each kernel is defined (and its
+// template instantiations made) in its own translation unit; the launch goes
+// through the host stub that unit emits.
 #pragma once
 
 #include "film_query.h"

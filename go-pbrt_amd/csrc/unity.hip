@@ -1,9 +1,10 @@
 // unity.hip — every translation unit of the library as one, for the diagnostics
 // and experiment builds (Makefile: steptime, meshcount, diag, variant), whose
-// __device__ counters must exist once. The kernel definitions come before
-// render.hip: their launch bounds must be on the first declaration a kernel
-// sees (render_kernels.h's plain declarations first would leave every kernel
-// at the default 1024-thread bound, i.e. 128 VGPRs, and spilling).
+// __device__ counters must exist once. The kernel definitions come before the
+// host units (kernel_select.hip, render.hip, queries.hip, diag.hip, group.hip):
+// their launch bounds must be on the first declaration a kernel sees
+// (render_kernels.h's plain declarations first would leave every kernel at the
+// default 1024-thread bound, i.e. 128 VGPRs, and spilling).
 #include "mesh_bvh.hip"
 #include "k_chain_1.hip"
 #include "k_chain_n.hip"
@@ -22,5 +23,8 @@
 #include "k_li_direct.hip"
 #include "k_path_step.hip"
 #include "k_film_q.hip"
+#include "kernel_select.hip"
 #include "render.hip"
+#include "queries.hip"
+#include "diag.hip"
 #include "group.hip"

@@ -193,7 +193,7 @@ def kernel_names():
 
 
 def kernel_choice(family, *args):
-    """The kernel render.hip's selector of `family` gives for these template arguments, by its
+    """The kernel the selector (kernel_select.hip) of `family` gives for these template arguments, by its
     launch-log name, or None if it is not compiled (pbrt_diag_kernel_choice; needs no GPU)."""
     abi.declare_kernel_choice(lib())
     a = (C.c_int * max(len(args), 1))(*[int(x) for x in args])

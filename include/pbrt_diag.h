@@ -138,7 +138,7 @@ int64_t pbrt_gpu_launch_log(struct pbrt_gpu_ctx* ctx, int which, pbrt_launch_rec
 /* Every name the log can produce (needs no GPU). Copies min(n, names) pointers
  * and returns the name count. */
 int pbrt_gpu_kernel_names(const char** out, int n);
-/* The answer of render.hip's kernel selectors, which every launch of a templated
+/* The answer of the kernel selectors (kernel_select.hip), which every launch of a templated
  * family goes through (needs no context and no GPU): the launch-log name of the
  * instantiation with exactly the template arguments `args`, or NULL if no unit
  * compiles it (a launch site then refuses with PBRT_E_HIP). Families and their n
@@ -203,7 +203,7 @@ int pbrt_gpu_mesh_download(struct pbrt_gpu_ctx* ctx, void* nodes, int32_t* gid, 
 
 /* Mesh-traversal counters of libraries built with -DPBRT_MESH_COUNT (make
  * meshcount; 0 values otherwise): [8 kernel slots][closest, any][walks, nodes
- * fetched, triangles tested], slots as render.hip's with_slot(). Returns the
+ * fetched, triangles tested], slots as with_slot()'s (context.h). Returns the
  * count (48), or 0 in a normal build. */
 int pbrt_gpu_mesh_counters(uint64_t* out, int n, int reset);
 

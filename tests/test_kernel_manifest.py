@@ -31,7 +31,7 @@ def test_manifest_reads_every_family():
     assert len(fam["k_chain_ci"]) > 20
     for k in fam["k_chain_ci"]:   # every argument spelled
         assert re.fullmatch(r"k_chain_ci<(1|2|4|8), (-1|0|64), (true|false), (0|2), (true|false), (true|false)>", k), k
-    assert MANIFEST["k_probe"] == "render.hip" and MANIFEST["k_flatten"] == "mesh_bvh.hip"
+    assert MANIFEST["k_probe"] == "diag.hip" and MANIFEST["k_flatten"] == "mesh_bvh.hip"
 
 
 def test_parser_on_a_synthetic_unit(tmp_path):

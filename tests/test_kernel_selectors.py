@@ -1,4 +1,4 @@
-"""render.hip's kernel selectors against the manifest of compiled kernels. No GPU.
+"""The kernel selectors (kernel_select.hip) against the manifest of compiled kernels. No GPU.
 
 Every launch of a templated family takes its kernel from one host function
 (chain_kernel, paths_ci_kernel, paths_cam_kernel, serial_kernel), which returns

@@ -54,7 +54,7 @@ def test_li_query_header_under_sanitizers(tmp_path):
 
 
 def test_selector_has_the_four_kernels_the_table_can_ask_for():
-    """li_kernel (render.hip) by its launch-log names; null for what is not compiled."""
+    """li_kernel (kernel_select.hip) by its launch-log names; null for what is not compiled."""
     for kx in (0, 1):
         for depth in (0, 64):
             assert G.kernel_choice("k_li", kx, depth) == f"k_li<{'true' if kx else 'false'}, {depth}>"

@@ -48,7 +48,7 @@ def test_path_query_header_under_sanitizers(tmp_path):
 
 
 def test_selector_has_the_four_kernels_the_table_can_ask_for():
-    """path_step_kernel (render.hip) by its launch-log names; null for what is not compiled."""
+    """path_step_kernel (kernel_select.hip) by its launch-log names; null for what is not compiled."""
     want = set()
     for kx in (0, 1):
         for depth in (0, 64):

@@ -4,8 +4,10 @@ arch VGPRs, AccVGPRs, SGPRs, scratch bytes per lane, static LDS, and the
 waves/SIMD the register file allows (512 registers per SIMD lane on CDNA4,
 shared by arch and acc VGPRs, allocated in granules of 8).
 
-    hipcc --offload-arch=gfx950 <Makefile FLAGS> --cuda-device-only -S -o /tmp/render.s csrc/render.hip
-    python tools/kernel_resources.py /tmp/render.s [name-filter ...] > profiles/r03/kernel_resources.json
+    make -C go-pbrt_amd asm      # build/asm/<unit>.s of every kernel unit (k_*.hip); for k_probe, the same
+                                 # hipcc line on csrc/diag.hip: hipcc --offload-arch=gfx950 <Makefile FLAGS>
+                                 # --cuda-device-only -S -o build/asm/diag.s csrc/diag.hip
+    python tools/kernel_resources.py go-pbrt_amd/build/asm/k_li.s [name-filter ...] > profiles/<change>/kernel_resources.json
 """
 import json
 import re
