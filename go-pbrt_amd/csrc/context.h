@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/pbrt_gpu.h"
+#include "frame_route.h"
 #include "knobs.h"
 #include "query_buffers.h"
 #include "render_common.h"
@@ -72,11 +73,7 @@ class DevBuf {
 struct pbrt_gpu_ctx {
     pbrtk::Knobs knobs;
     int device = 0;
-    struct {
-        int n_simd = 1024;                 // SIMDs of the device (4 per CU)
-        size_t lds_per_block = 65536;      // the device's LDS limit per workgroup (sharedMemPerBlock)
-        size_t lds_per_cu = 160 * 1024;    // LDS of a CU (maxSharedMemoryPerMultiProcessor)
-    } dev;
+    pbrtroute::Facts facts;   // what the frame's rules read of the scene and the device (pbrt_gpu_create)
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
     // heavy/light split of k_chain_ci: the heaviest tiles with 4 waves each on
@@ -129,23 +126,24 @@ struct pbrt_gpu_ctx {
     int min_waves = 1;      // amdgpu_waves_per_eu variant of k_render_exact
     int occ_req = 0;        // opts.occupancy as given (0 = each kernel's default)
     int kernel_req = PBRT_KERNEL_AUTO;
-    int last_kernel = 0;    // PBRT_KERNEL_SERIAL / PBRT_KERNEL_WAVE
+    int last_kernel = 0;    // stats.kernel of the last frame (pbrtroute::last_kernel of its route)
     DevBuf<pbrtk::PcgJump> d_jump;
     pbrt_distribution_desc host_dist;
+    // the last frame's route (frame_route.h) and what it fixes for every launch: whether the scene
+    // is triangle meshes only, and the dynamic-LDS layouts of k_mb_setup (L), k_chain_ci /
+    // k_dl_setup (Lci) and k_chain_cam / k_cam_setup (Lcam)
+    pbrtroute::Route route = pbrtroute::Route::Serial;
+    bool mesh_only = false;
+    struct {
+        pbrtk::ChainLayout L{}, Lci{}, Lcam{};
+    } lay;
     // wave-parallel path (k_wf_primary, k_chain_ci, k_paths_ci / k_pw_*, k_film)
-    pbrtk::ChainLayout lay{};
-    bool use_spec = false;
     DevBuf<unsigned char> d_wave;      // per-batch pixel records, stratified values, RNG states, L
     int64_t wave_batch = 0;            // tile slots per batch
     int tiles_per_wave = 1;            // k_chain_ci lane groups per wave (64 / lanes per tile)
     std::vector<hipEvent_t> bev;       // per batch: before the chain, after the chain, after the paths
     int n_batches = 0;
     pbrtk::WaveBufs wb{};
-    bool use_ci = false;   // the Path chain stage (k_chain_ci)
-    bool use_dl = false;   // DirectLighting on k_dl_setup / k_dl_samples
-    pbrtk::ChainLayout lay_ci{};
-    bool use_cam = false;   // the camera-start route (PBRT_KERNEL_WAVE_CAM: k_chain_cam, k_paths_cam, k_film_cam)
-    pbrtk::ChainLayout lay_cam{};
     // device scene
     DevBuf<pbrt_shape_desc> d_shapes;
     DevBuf<pbrt_material_desc> d_materials;
@@ -163,8 +161,6 @@ struct pbrt_gpu_ctx {
     DevBuf<pbrt_distribution_desc> d_dist;
     pbrt_scene_desc host_scene;   // counts + film/camera (pointer fields are not kept)
     std::vector<pbrt_light_desc> host_lights;
-    bool non_matte = false;       // Mirror, Glass or OrenNayar material: kX wave kernels or the serial kernel
-    bool rough_glass = false;     // a Glass material with roughness: serial kernel only
     // per-render buffers (grown on demand)
     DevBuf<double> d_films;
     DevBuf<double> d_s1d;

@@ -230,7 +230,7 @@ extern "C" int64_t pbrt_gpu_launch_log(pbrt_gpu_ctx* c, int which, pbrt_launch_r
     return m;
 }
 
-extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->dev.lds_per_block : -PBRT_E_INVALID; }
+extern "C" int64_t pbrt_gpu_lds_per_block(pbrt_gpu_ctx* c) { return c ? (int64_t)c->facts.lds_per_block : -PBRT_E_INVALID; }
 
 extern "C" int pbrt_gpu_schedule_source(pbrt_gpu_ctx* c) {
     if (!c) return -PBRT_E_INVALID;

@@ -1,6 +1,6 @@
 // li_query.h — the host side of pbrt_gpu_li_device (include/pbrt_gpu.h) that
 // needs no device: the argument checks, the conditions under which path_step is
-// not the reference (wave_eligible's, render.hip), and the choice of the k_li
+// not the reference (wave_eligible's, frame_route.h), and the choice of the k_li
 // instantiation and its grid from the scene.
 // Plain C++ with no dependency on HIP: queries.hip passes in what it knows of
 // the context, and tests/li_query_check.cpp compiles this header on its own.

@@ -28,6 +28,7 @@
 
 #include "pbrt_path.h"
 #include "pcg_jump.h"
+#include "render_params.h"   // kMaxCachedLights
 #include <type_traits>
 
 namespace pbrt {
@@ -135,7 +136,6 @@ __host__ __device__ __forceinline__ uint32_t camera_draws(int ndims) {
     return (ndims < 1 ? 2u : 0u) + (ndims < 2 ? 2u : 0u) + (ndims < 1 ? 1u : 0u);
 }
 
-constexpr int kMaxCachedLights = 16;
 // a cached bounce-1 light estimate traced its visibility ray (ray counters;
 // or-ed into the estimate's panic word, whose low 16 bits are the panic kind)
 constexpr int kLdTraced = 0x10000;

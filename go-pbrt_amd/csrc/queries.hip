@@ -196,13 +196,13 @@ int pbrt_gpu_li_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_so
     const char* why = "";
     if (int rc = pbrtli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
         return set_err(c, rc, why);
-    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtli::check_supported(*d, c->facts.rough_glass, &why)) return set_err(c, rc, why);
     if (int rc = li_distribution(c, d, n)) return rc;
     if (n == 0) return PBRT_OK;
     DevScene sc;
     if (int rc = query_begin(c, true, sc)) return rc;
     const pbrtli::KernelArgs ka =
-        pbrtli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
+        pbrtli::kernel_args(c->facts.non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
     const LiKernel kern = li_kernel(ka.kx, ka.depth);
     if (!kern) return set_err(c, PBRT_E_HIP, "no k_li instantiation for depth " + std::to_string(ka.depth));
     launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
@@ -229,13 +229,13 @@ int pbrt_gpu_path_step_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt
     const char* why = "";
     if (int rc = pbrtpath::check_step(c != nullptr, d, paths, in, out, n, c && query_blocked(c), &why))
         return set_err(c, rc, why);
-    if (int rc = pbrtli::check_supported(*d, c->rough_glass, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtli::check_supported(*d, c->facts.rough_glass, &why)) return set_err(c, rc, why);
     if (int rc = li_distribution(c, d, n)) return rc;
     if (n == 0) return PBRT_OK;
     DevScene sc;
     if (int rc = query_begin(c, true, sc)) return rc;
     const pbrtli::KernelArgs ka =
-        pbrtpath::step_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
+        pbrtpath::step_args(c->facts.non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
     const PathStepKernel kern = path_step_kernel(ka.kx, ka.depth);
     if (!kern) return set_err(c, PBRT_E_HIP, "no k_path_step instantiation for depth " + std::to_string(ka.depth));
     if (out) HIPCHK(c, hipMemsetAsync(out->count, 0, sizeof(uint32_t), c->stream));
@@ -252,11 +252,11 @@ int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* c, const pbrt_direct_li_desc* d, con
     const char* why = "";
     if (int rc = pbrtdli::check_args(c != nullptr, d, rays, rng, n, out, c && query_blocked(c), &why))
         return set_err(c, rc, why);
-    if (int rc = pbrtdli::check_supported(*d, c->rough_glass, c->non_matte, &why)) return set_err(c, rc, why);
+    if (int rc = pbrtdli::check_supported(*d, c->facts.rough_glass, c->facts.non_matte, &why)) return set_err(c, rc, why);
     if (n == 0) return PBRT_OK;
     DevScene sc;
     if (int rc = query_begin(c, false, sc)) return rc;
-    const pbrtdli::KernelArgs ka = pbrtdli::kernel_args(c->non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n,
+    const pbrtdli::KernelArgs ka = pbrtdli::kernel_args(c->facts.non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n,
                                                         kLdsNodes, c->knobs.direct_li_grid, d->max_depth);
     const DirectLiKernel kern = direct_li_kernel(ka.kx, ka.depth);
     if (!kern) return set_err(c, PBRT_E_HIP, "no k_li_direct instantiation for depth " + std::to_string(ka.depth));

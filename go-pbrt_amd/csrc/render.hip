@@ -1,13 +1,18 @@
 // render.hip — a context's life and its frame: scene upload (pbrt_gpu_create),
-// launch planning and the frame's stages (render_enqueue, pbrt_gpu_synchronize),
+// the frame's stages (render_enqueue, pbrt_gpu_synchronize; what they launch: frame_route.h),
 // the film's way out. The host side of the MI355X (gfx950) library by unit:
 //   context.h          what every unit below needs: HIPCHK, DevBuf, pbrt_gpu_ctx,
 //                      set_err, launch_k, dev_scene, with_slot, query_blocked
 //   kernel_select.hip  the selectors (kernel_select.h: arguments in, the host
 //                      pointer of that instantiation out) and the launch log's names
-//   render.hip         create / destroy / cancel / last_error; eligibility and LDS
-//                      layouts, prepare, the frame's stages, synchronize, render;
-//                      film_download, pbrt_film_to_rgba8, the group's member view
+//   frame_route.h      the rules that decide what a frame launches, pure and HIP-free
+//                      (render_params.h: what they hand the kernels): the desc's check,
+//                      RenderParams, the route and its refusals, the LDS layouts, the
+//                      chain and path launches' arithmetic, the buffers' carving
+//   render.hip         create / destroy / cancel / last_error; prepare and the frame's
+//                      stages (their HIP calls; their numbers are frame_route.h's),
+//                      synchronize, render; film_download, pbrt_film_to_rgba8, the
+//                      group's member view
 //   queries.hip        everything a context answers between frames: ray queries,
 //                      camera rays, Li / DirectLighting.Li / Path.Li by steps, a
 //                      frame from public pieces, the context's buffers
@@ -57,6 +62,7 @@
 #include "../../include/pbrt_diag.h"
 #include "../../include/pbrt_scene.h"
 #include "context.h"
+#include "frame_route.h"
 #include "kernel_select.h"
 #include "scene_tables.h"
 #include "schedule.h"
@@ -109,7 +115,7 @@ namespace {
 // the process cache's key (schedule.h) of a schedule key on this context's scene and device
 uint64_t sched_cache_key(const pbrt_gpu_ctx* c, uint64_t skey) {
     uint64_t h = fnv_bytes(c->scene_hash, &skey, sizeof(skey));
-    return fnv_bytes(h, &c->dev.n_simd, sizeof(c->dev.n_simd));   // the device's size shapes the split
+    return fnv_bytes(h, &c->facts.n_simd, sizeof(c->facts.n_simd));   // the device's size shapes the split
 }
 
 std::vector<DevNode> dev_nodes(const pbrt_scene_desc* s) {
@@ -151,325 +157,45 @@ const PcgJump& pcg_jump_table() {
     return J;
 }
 
-int paths_ci_pixels(const pbrt_gpu_ctx* c, const RenderParams& rp);
-bool paths_wf_enabled(const pbrt_gpu_ctx* c);
-// Offsets into a kernel's dynamic LDS block, handed out in order, each 16-byte aligned.
-struct LdsCarve {
-    int64_t off = 0;
-    int put(int64_t bytes) {
-        const int64_t o = off;
-        off += (bytes + 15) & ~int64_t(15);
-        return (int)o;
-    }
-};
-// A light the distribution never picks (pdf 0) changes the draw count of a light sample.
-bool zero_pdf_light(const pbrt_distribution_desc& d) {
-    if (!(d.func_int > 0)) return true;
-    for (int i = 0; i < d.count; i++)
-        if (!(d.func[i] > 0)) return true;
-    return false;
-}
-// Can the wave-parallel kernels replay this render exactly? (conditions: pbrt_spec.h)
-#ifndef PBRT_SP_SERIAL_KB
-// above this many KB of raw StartPixel draws, StartPixel runs on one lane and
-// its buffers leave LDS (build option). 4: config C's 256-spp pixels (9.5 KB
-// of draws) then cost a k_chain_ci workgroup 11 KB of LDS instead of 27, 12
-// workgroups share a CU and the chain runs the 3-wave build: C 6.50 -> 5.14 s
-// (a pixel's serial StartPixel, ~20 us, is under 0.5% of a C tile's chain)
-#define PBRT_SP_SERIAL_KB 4
-#endif
-#ifndef PBRT_SP_WINDOW_KB
-#define PBRT_SP_WINDOW_KB 6   // LDS for the windowed StartPixel's picks, permutations and draw ring (build option)
-#endif
-#ifndef PBRT_CI_STAGE_KB
-#define PBRT_CI_STAGE_KB 8   // k_chain_ci stages StartPixel's stratified values in LDS up to this (build option)
-#endif
-bool wave_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const RenderParams& rp, ChainLayout& L,
-                   ChainLayout& Lci) {
-    if (rd->flags & PBRT_FLAG_PANIC_FIDELITY) return false;   // the serial kernel traces the extra rays
-    const bool dl = rd->integrator == PBRT_INTEGRATOR_DIRECT_LIGHTING;
-    // Mirror, smooth Glass and OrenNayar: Path renders run the kX instantiations
-    // of the wave pipeline (trajectories and paths over BSDFX, with etaScale):
-    // k_chain_ci (kDepth 0 for LDS-staged trees, the [64] stack beyond), then
-    // k_paths_ci (P = 4, 8) or the path wavefront (mesh scenes, trees beyond
-    // kLdsNodes, more than 16 lights); rough glass (whose every BSDF sample
-    // panics) stays on the serial kernel. THROUGHPUT mode has no chain: its
-    // k_mb_setup<true> and the kX path wavefront walk any tree
-    // DirectLighting over these materials runs k_dl_samples<kX> (the recursion per
-    // sample; maxDepth <= 64 as the serial kernel), rough glass stays serial
-    if (c->non_matte && (c->rough_glass || (dl && rd->max_depth > 64) ||
-                         (!dl && !paths_wf_enabled(c) && paths_ci_pixels(c, rp) > 0 && paths_ci_pixels(c, rp) < 4)))
-        return false;
-    if (dl) {   // k_dl_*: the camera ray must be per pixel (pFilm stratified; pLens stratified or unused)
-        if (rd->n_dims < 1 || (rd->n_dims < 2 && c->host_scene.camera.lens_radius > 0)) return false;
-    } else if (rd->integrator != PBRT_INTEGRATOR_PATH || rd->max_depth > 2048) {
-        return false;   // D < 2^32
-    } else if (rd->n_dims < 2 && !(rd->n_dims == 1 && c->host_scene.camera.lens_radius == 0)) {
-        // the camera ray must be the pixel's (k_wf_primary): pFilm stratified
-        // (n_dims >= 1), and pLens stratified (n_dims >= 2) or unused (a pinhole)
-        return false;
-    }
-    const int nl = c->host_scene.n_lights;
-    // (any light count: beyond the kMaxCachedLights of PixelCache::ld[] paths_ci_pixels answers 0
-    // and the path wavefront runs the paths; its k_pw_cache writes global arrays of n_lights per pixel)
-    if (!dl && nl > 0 && zero_pdf_light(c->host_dist)) return false;
-    // k_film stages the tile film's running sums and a run of source pixels in LDS
-    // (any filter radius below the tile size: footprints beyond 2x2 included)
-    // (+ its static per-run nvalid array, k_frame.hip)
-    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->dev.lds_per_block) return false;
-    const int64_t n = rp.spp, nd = rp.ndims;
-    if (n > 4096 || nd * n > 8192) return false;
-    LdsCarve lds;
-    L.s1d = lds.put(nd * n * 8);
-    L.other = lds.put(nd * n * 2);
-    L.sbuf = lds.put(kWave * 8);
-    L.dbuf = lds.put(kWave * 4);
-    L.vbuf = lds.put(sp_vbuf_bytes(rp));
-    L.total = (int)lds.off;
-    L.ring = 0;
-    // k_chain_ci: the same staging without the window buffers, then the ring
-    lds = LdsCarve{};
-    // the pixel's stratified values are staged in LDS while the staging of one
-    // 1-wave tile (aliased with the ring) stays <= PBRT_CI_STAGE_KB; above,
-    // StartPixel writes them straight to the pixel's global record (always with
-    // the serial StartPixel, large spp): the trajectories read them from there
-    // anyway, and a smaller workgroup lets more share a CU (config C at 8 KB:
-    // 6.50 -> 5.25 s)
-    const int64_t al16 = 15;
-    const int64_t lds_staging = ((nd * n * 8 + al16) & ~al16) + ((nd * n * 2 + al16) & ~al16) +
-                                ((sp_vbuf_bytes(rp) + al16) & ~al16);
-    if (rp.sp_window) {   // the windowed StartPixel: picks in LDS, values straight to the global record
-        Lci.s1d = -1;
-        Lci.other = lds.put(nd * n * 2);
-    } else if (rp.sp_serial) {
-        Lci.s1d = -1;
-        Lci.other = lds.put(16);
-    } else if (lds_staging > PBRT_CI_STAGE_KB * 1024) {
-        Lci.s1d = -1;
-        Lci.other = lds.put(nd * n * 2);
-    } else {
-        Lci.s1d = lds.put(nd * n * 8);
-        Lci.other = lds.put(nd * n * 2);
-    }
-    Lci.sbuf = Lci.dbuf = 0;
-    Lci.vbuf = lds.put(sp_vbuf_bytes(rp));
-    Lci.staging = (int)lds.off;
-    Lci.ring = lds.put(kCiRingBytes);
-    Lci.total = (int)lds.off;
-    return L.total <= 48 * 1024;
-}
+// sizeof of the device structs frame_route.h counts in
+constexpr pbrtroute::Sizes kSizes{sizeof(ChainCache), sizeof(PixelRec), sizeof(PanicRec), sizeof(RrBranches),
+                                  sizeof(PwPath),     sizeof(Spec),     sizeof(RingEnt)};
+static_assert(pbrtroute::kDlMaxDepthX == 2 * kDlMaxLevels, "check_render's DirectLighting depth is k_dl_samples<kX>'s");
 
-// Can the camera-start route (PBRT_KERNEL_WAVE_CAM) replay this render exactly?
-// It takes the renders whose camera ray belongs to the sample: n_dims == 0, or
-// n_dims == 1 with a thin lens (cam_sample.h). Path integrator, Matte scenes on a
-// tree of any size (beyond kLdsNodes: the k_*_cam_stack kernels), any light count
-// (the route has no bounce-1 cache: every light sample is estimated where it is
-// drawn); otherwise wave_eligible's conditions. `why` names the reason
-// of a refusal. L: k_chain_cam's / k_cam_setup's dynamic LDS (the StartPixel
-// staging of n_dims == 1, aliased with the offset ring).
-bool wave_cam_eligible(const pbrt_gpu_ctx* c, const pbrt_render_desc* rd, const RenderParams& rp, ChainLayout& L,
-                       std::string& why) {
-    auto no = [&](const char* m) {
-        why = m;
-        return false;
-    };
-    if (rd->flags & PBRT_FLAG_PANIC_FIDELITY) return no("panic fidelity runs on the serial kernel");
-    if (rd->integrator != PBRT_INTEGRATOR_PATH) return no("Path integrator only (DirectLighting is out of scope)");
-    if (rd->max_depth > 2048) return no("maxDepth > 2048");
-    if (rd->n_dims >= 2) return no("n_dims >= 2: the camera ray is the pixel's (the wave_ci route)");
-    if (rd->n_dims == 1 && !(c->host_scene.camera.lens_radius > 0))
-        return no("n_dims == 1 with a pinhole: the camera ray is the pixel's (the wave_ci route)");
-    if (c->non_matte) return no("Mirror / Glass / OrenNayar materials");
-    if (c->mesh.n_nodes != 0) return no("triangle meshes");
-    const int nl = c->host_scene.n_lights;
-    if (nl > 0 && zero_pdf_light(c->host_dist)) return no("a light with pdf 0");
-    if ((size_t)film_lds_bytes(rp) + kFilmThreads * sizeof(int) > c->dev.lds_per_block)
-        return no("the tile film does not fit LDS");
-    const int64_t n = rp.spp, nd = rp.ndims;
-    if (n > 4096 || nd * n > 8192) return no("more than 4096 samples per pixel");
-    LdsCarve lds;
-    L = ChainLayout{};
-    // (large spp: the serial StartPixel writes straight to the pixel's global record)
-    L.s1d = rp.sp_serial || nd == 0 ? -1 : lds.put(nd * n * 8);
-    L.other = lds.put(rp.sp_serial ? 16 : nd * n * 2 + 16);
-    L.vbuf = lds.put(rp.sp_serial ? 4 : sp_vbuf_bytes(rp));
-    L.staging = (int)lds.off;
-    L.ring = 0;
-    L.total = std::max((int)lds.off, kCiRingBytes);
-    return true;
-}
-
-// k_chain_ci's LDS layout for w waves per tile and G tiles per wave. With one
-// tile per workgroup (G == 1) the StartPixel staging aliases the offset ring:
-// a group starts a pixel only after its chain has dropped every candidate,
-// so the two are never live together (config C, 256 spp: 19 KB of staging).
-// Multi-wave Matte tiles (nps: k_chain_ci's next-pixel speculation) keep
-// trajectories of the next pixel in flight through its StartPixel: two rings
-// (one per pixel parity) after the staging.
-ChainLayout ci_layout(const ChainLayout& base, int w, int G, unsigned& lds_bytes, bool nps = false) {
-    ChainLayout l = base;
-    if (nps) {
-        l.ring = (base.staging + 15) & ~15;
-        lds_bytes = (unsigned)(l.ring + 2 * w * kCiRingBytes);
-    } else if (G == 1) {
-        l.ring = 0;
-        lds_bytes = (unsigned)std::max(base.staging, w * kCiRingBytes);
-    } else {
-        lds_bytes = (unsigned)(base.total + (w - 1) * kCiRingBytes);
-    }
-    // then two ChainCache per lane group (pixel parities; only the groups in use: G, not kCiMaxGroups)
-    l.pcs = (int)((lds_bytes + 15u) & ~15u);
-    lds_bytes = (unsigned)l.pcs + (unsigned)(2 * G * sizeof(ChainCache));
-    l.total = (int)lds_bytes;
-    return l;
-}
-
-// Waves per tile of k_chain_ci for a launch of nb tiles. The frame's EXACT
-// time is bounded below by its slowest tile's chain, so when the tiles of a
-// launch cannot keep every wave slot busy (2 waves/SIMD) a tile gets 2 or 4
-// waves. PBRT_CI_WAVES (1, 2, 4) overrides.
-int ci_waves(const pbrt_gpu_ctx* c, int64_t nb) {
-    if (c->knobs.ci_waves) return c->non_matte ? std::min(c->knobs.ci_waves, 4) : c->knobs.ci_waves;
-    if (c->tiles_per_wave > 1) return 1;
-    // measured on config B shards (tools/shard_sim.py): 8160 tiles -> 1,
-    // 4080 -> 2, 2040 and 1020 -> 4
-    const int64_t slots = (int64_t)c->dev.n_simd * 2;   // 2 waves/SIMD
-    if (nb <= slots) return 4;
-    if (nb <= 2 * slots) return 2;
-    return 1;
-}
-
-// k_chain_ci schedule. An EXACT frame lasts at least as long as its slowest
-// tile's chain, and workgroups start in launch order, so a heavy tile that
-// starts late stretches the frame. Each EXACT frame records every tile's
-// chain time; the next frame of the same configuration on this context
-// launches its tiles heaviest first (LPT). Only the schedule changes, never
-// a result. PBRT_CI_ORDER=0 disables it.
-// Multi-GPU shards (launches that would run 2 or 4 waves per tile): the
-// heaviest tiles of the previous frame get 4 waves in a launch of their own
-// and the rest 1 wave each in a concurrent one (1/4- and 1/2-frame shards:
-// 387 -> 305 ms and 524 -> 472 ms per rank). PBRT_CI_SPLIT=0 disables it;
-// PBRT_CI_HEAVY=K forces the heavy count (tests).
-bool ci_split_enabled(const pbrt_gpu_ctx* c) { return c->knobs.ci_split; }
-// Does a one-wave Matte k_chain_ci workgroup with `dyn_lds` bytes of dynamic
-// LDS leave room for 3 waves per SIMD (12 workgroups on a CU's LDS)?
-// (`multi`: the several-tiles-per-wave instantiation, whose static LDS differs)
-bool ci_eu3_fits(const pbrt_gpu_ctx* c, unsigned dyn_lds, bool lds_nodes, bool multi = false) {
+// Static LDS of the one-wave Matte k_chain_ci of this context's tree, the 3-waves/SIMD build
+// (`multi`: the several-tiles-per-wave instantiation, whose static LDS differs); 0 on failure.
+size_t ci_static_lds(const pbrt_gpu_ctx* c, bool multi) {
     hipFuncAttributes fa;
-    const void* f = reinterpret_cast<const void*>(chain_kernel(1, lds_nodes ? 0 : 64, false, 0, false, multi));
-    size_t stat = 0;
-    if (hipFuncGetAttributes(&fa, f) == hipSuccess) stat = fa.sharedSizeBytes;
-    const size_t per_wg = stat + dyn_lds;
-    return per_wg > 0 && c->dev.lds_per_cu / per_wg >= 12;
-}
-int64_t ci_heavy_override(const pbrt_gpu_ctx* c) { return c->knobs.ci_heavy; }
-// k_chain_ci candidate stride: 2 issues candidates at the chain head's parity
-// only (dropped when an odd draw count flips it), 1 at every offset (twice
-// the candidates, none dropped). PBRT_CI_STRIDE = 1 / 2 overrides.
-int ci_stride(const pbrt_gpu_ctx* c, int w) {
-    if (c->knobs.ci_stride) return c->knobs.ci_stride;
-    return w > 1 ? 1 : 2;
-}
-// PBRT_CI_HEAVY_WAVES = 4 (default) or 8: waves per heavy tile of the split
-int ci_heavy_waves(const pbrt_gpu_ctx* c) { return c->non_matte ? 4 : c->knobs.ci_heavy_waves; }
-bool ci_order_enabled(const pbrt_gpu_ctx* c) { return c->knobs.ci_order; }
-// PBRT_CI_ORDER_CACHE=0: no process-wide schedule cache (each context learns its own)
-bool ci_order_cache(const pbrt_gpu_ctx* c) { return c->knobs.ci_order_cache; }
-// PBRT_CI_PROBE=0: a fresh context's first frame runs in launch order (no k_tile_cost)
-bool ci_probe_enabled(const pbrt_gpu_ctx* c) { return c->knobs.ci_probe; }
-uint64_t schedule_key(const RenderParams& rp, int kw) {
-    const int64_t v[] = {rp.film_min_x, rp.film_min_y, rp.film_w,   rp.film_h,    rp.tile_size, rp.tile_begin,
-                         rp.tile_stride, rp.n_slots,   rp.spp,      rp.ndims,     rp.jitter,    rp.max_depth,
-                         rp.flags,       kw,           (int64_t)(rp.rr_threshold * 1e9)};
-    uint64_t h = 1469598103934665603ull;
-    for (int64_t x : v) h = (h ^ (uint64_t)x) * 1099511628211ull;
-    return h;
+    const void* f = reinterpret_cast<const void*>(
+        chain_kernel(1, c->facts.n_nodes <= kLdsNodes ? 0 : 64, false, 0, false, multi));
+    return hipFuncGetAttributes(&fa, f) == hipSuccess ? fa.sharedSizeBytes : 0;
 }
 
-// k_paths_ci (lane refill over kPathsPixels pixels per wave) where it fits:
-// LDS-staged nodes, the pixels' stratified values in 16 KB of LDS and one
-// lane per (pixel, light) for the bounce-1 estimates; 0: the path wavefront
-// (k_pw_*) runs the paths. PBRT_PATHS_CI=0 forces that.
-// Returns the pixels per wave (2, 4 or 8; PBRT_PATHS_CI overrides, 0 = off).
-// k_paths_ci stages the stratified values of its P pixels in LDS when they take <= 16 KB
-// Off by default: read from their global records (L2-resident; config B
-// 111.0 -> 109.9 ms EXACT, 136.0 -> 134.8 ms THROUGHPUT against LDS staging).
-// PBRT_PATHS_S1D=lds stages them where they fit (experiments).
-bool paths_ci_s1d_lds(const pbrt_gpu_ctx* c, const RenderParams& rp, int P) {
-    return c->knobs.paths_s1d_lds && (int64_t)P * rp.ndims * rp.spp * 8 <= 16 * 1024;
-}
-int paths_ci_pixels(const pbrt_gpu_ctx* c, const RenderParams& rp) {
-    int pp = 4;
-    bool forced = false;
-    if (c->knobs.paths_ci == 0) return 0;
-    if (c->knobs.paths_ci > 0) pp = c->knobs.paths_ci, forced = true;
-    auto fits = [&](int p) {   // (kMaxCachedLights: PixelCache::ld[]; a forced P = 2 would admit up to 32 lights)
-        return c->host_scene.n_nodes <= kLdsNodes && p * c->host_scene.n_lights <= kWave &&
-               c->host_scene.n_lights <= kMaxCachedLights;
-    };
-    if (forced) return fits(pp) ? pp : 0;
-    // 8 pixels per wave where their lights fit one wave, else 4; stratified
-    // values read from global memory (config B EXACT paths 109.9 -> 104.8 ms
-    // for 8 against 4; config C at 256 spp 872 -> 869 ms, where 4 pixels with
-    // global values already beat 2 with LDS values, 1150 ms)
-    return fits(8) ? 8 : fits(4) ? 4 : 0;
-}
-
-// The full-path stage on the path wavefront (k_pw_*) instead of k_paths_ci:
-// PBRT_PATHS_WF=1 / 0 forces it on / off; by default it runs for scenes with
-// triangle meshes, where it measured faster (config D: 385 -> 343 ms EXACT,
-// 420 -> 381 ms THROUGHPUT), and not for the analytic scenes, where the
-// monolithic lane-refill kernel is twice as fast (config B: 118 vs 212-245 ms;
-// profiles/r02/path_wavefront_ab.json). PBRT_PW_SORT=1 adds the material sort
-// between trace and shade: a loss on every scene measured (B 212 -> 245 ms: a
-// few matte materials leave no shading divergence to remove), so off by default.
-// Triangle meshes and no analytic primitive: the kMeshOnly kernels (k_chain_ci
-// kDepth < 0, k_pw_trace / k_pw_shadow<true>) compile the analytic walk out.
-bool mesh_only_scene(const pbrt_gpu_ctx* c) {
-    return c->host_scene.n_prims == 0 && c->mesh.n_nodes > 0 && !c->non_matte;
-}
-
-bool paths_wf_enabled(const pbrt_gpu_ctx* c) {
-    if (c->knobs.paths_wf >= 0) return c->knobs.paths_wf == 1;
-    return c->mesh.n_nodes > 0;
-}
+// The path wavefront (k_pw_*) over the batch's pixel records, in chunks (pbrtroute::pw_carve).
 int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb) {
     const RenderParams& rp = c->rp;
     const int64_t nrec = nb * c->wb.ppt, per = rp.spp - 1;
     const int nl = sc.n_lights;
     const int sort = c->knobs.pw_sort ? 1 : 0;
-    const int n_keys = std::max(1, std::min(c->host_scene.n_materials, kPwMaxKeys));
-    const double gb = c->knobs.pw_gb;
-    const int64_t per_path = (int64_t)sizeof(PwPath) + 4 * 4;   // record + 4 queue slots
-    int64_t chunk = per > 0 ? std::max<int64_t>(1, (int64_t)(gb * 1073741824.0) / (per_path * per)) : nrec;
-    chunk = std::min(chunk, nrec);
-    if (per > 0) chunk = std::min<int64_t>(chunk, (int64_t)0xFFFFFFF0 / per);
-    const int64_t cap = std::max<int64_t>(1, chunk * std::max<int64_t>(per, 1));
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
+    const int n_keys = std::max(1, std::min(c->facts.n_materials, kPwMaxKeys));
     const int64_t ncnt = 3 + 2 * kPwMaxKeys;
-    const size_t need = (size_t)(al(cap * (int64_t)sizeof(PwPath)) + 4 * al(cap * 4) + al(ncnt * 4) +
-                                 al(chunk * std::max(nl, 1) * (int64_t)sizeof(Spec)) + al(chunk * std::max(nl, 1) * 4) +
-                                 al(nrec * 8));
-    if (const int rc = c->d_pw.ensure(c, need)) return rc;
+    const pbrtroute::PwCarve pw = pbrtroute::pw_carve(c->knobs, c->facts, rp, kSizes, nrec, ncnt);
+    const int64_t chunk = pw.chunk;
+    if (const int rc = c->d_pw.ensure(c, pw.need)) return rc;
     unsigned char* p = c->d_pw.get();
-    auto take = [&](int64_t bytes) {
-        unsigned char* q = p;
-        p += al(bytes);
-        return q;
-    };
-    PwPath* paths = (PwPath*)take(cap * (int64_t)sizeof(PwPath));
+    PwPath* paths = (PwPath*)(p + pw.paths);
     PwQueues qs;
-    for (int i = 0; i < 3; i++) qs.q[i] = (uint32_t*)take(cap * 4);
-    qs.sorted = (uint32_t*)take(cap * 4);
-    qs.cnt = (uint32_t*)take(ncnt * 4);
-    qs.cap = cap;
-    Spec* ldc = (Spec*)take(chunk * std::max(nl, 1) * (int64_t)sizeof(Spec));
-    int* ldp = (int*)take(chunk * std::max(nl, 1) * 4);
-    unsigned long long* pkey = (unsigned long long*)take(nrec * 8);
-    const unsigned G = (unsigned)std::max<int64_t>(64, (int64_t)c->dev.n_simd * 8);   // grid-stride blocks
+    for (int i = 0; i < 3; i++) qs.q[i] = (uint32_t*)(p + pw.q[i]);
+    qs.sorted = (uint32_t*)(p + pw.sorted);
+    qs.cnt = (uint32_t*)(p + pw.cnt);
+    qs.cap = pw.cap;
+    Spec* ldc = (Spec*)(p + pw.ldc);
+    int* ldp = (int*)(p + pw.ldp);
+    unsigned long long* pkey = (unsigned long long*)(p + pw.pkey);
+    const unsigned G = (unsigned)std::max<int64_t>(64, (int64_t)c->facts.n_simd * 8);   // grid-stride blocks
     HIPCHK(c, hipMemsetAsync(pkey, 0xFF, (size_t)nrec * 8, c->stream));
     const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
-    const bool kx = c->non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
+    const bool kx = c->facts.non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
     for (int64_t r0 = 0; r0 < nrec; r0 += chunk) {
         const int64_t nr = std::min(chunk, nrec - r0);
         if (per > 0) {
@@ -483,7 +209,7 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
             launch_k(c, start, dim3((unsigned)((nr * per + kWave - 1) / kWave)), dim3(kWave), 0, c->stream,
                                sc, rp, c->wb, sb, r0, nr, ldc, ldp, paths, qs, pkey);
             for (int pass = 0; pass + 1 < rp.max_depth; pass++) {
-                launch_k(c, mesh_only_scene(c) ? k_pw_trace<true> : k_pw_trace<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, 0,
+                launch_k(c, c->mesh_only ? k_pw_trace<true> : k_pw_trace<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, 0,
                                    n_keys, pkey);
                 if (sort && n_keys > 1) {
                     launch_k(c, k_pw_scan, dim3(1), dim3(1), 0, c->stream, qs, n_keys);
@@ -492,7 +218,7 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
                 launch_k(c, kx ? k_pw_shade<true> : k_pw_shade<false>, dim3(G), dim3(kWave), 0, c->stream, sc,
                                    rp, c->wb, sb, paths, qs,
                                    sort && n_keys > 1 ? 1 : 0, pkey);
-                launch_k(c, mesh_only_scene(c) ? k_pw_shadow<true> : k_pw_shadow<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, pkey);
+                launch_k(c, c->mesh_only ? k_pw_shadow<true> : k_pw_shadow<false>, dim3(G), dim3(kWave), 0, c->stream, sc, rp, c->wb, paths, qs, pkey);
             }
         }
         launch_k(c, k_pw_panics, dim3((unsigned)((nr + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, sb, r0,
@@ -502,105 +228,37 @@ int paths_wavefront(pbrt_gpu_ctx* c, const DevScene& sc, int64_t sb, int64_t nb)
     return PBRT_OK;
 }
 
-// Carve the per-batch buffers of the wave path. Budget: PBRT_WAVE_BUFFER_GB,
-// default min(96 GB, half the free HBM) -- config C (1080p, 256 spp, ~34 GB)
-// and one rank's 1/8 shard of config E (4K, 1024 spp, ~68 GB) are then one
-// batch on a 288 GB MI355X, so the whole frame is one launch per kernel and
-// gets the heaviest-first schedule.
+// The per-batch buffers of the wave routes (pbrtroute::wave_carve sizes the batch and places the arrays).
 int wave_buffers(pbrt_gpu_ctx* c) {
-    const RenderParams& rp = c->rp;
-    const int64_t ppt = rp.tile_size * rp.tile_size, n = rp.spp, nd = rp.ndims > 0 ? rp.ndims : 1;
-    auto al = [](int64_t b) { return (b + 255) & ~int64_t(255); };
-    // k_chain_ci<kX>'s RR decision records, one per ring entry (Path renders of non-Matte scenes)
-    const int64_t rrb_bytes = c->non_matte ? (int64_t)kCiMaxRing * (int64_t)sizeof(RrBranches) : 0;
-    const int64_t per_tile = al(ppt * (int64_t)sizeof(PixelRec)) + al(ppt * nd * n * 8) + al(ppt * n * 8) +
-                             al(ppt * n * 24) + al(ppt * n * 4) + al(ppt * (int64_t)sizeof(PanicRec)) + al(4) +
-                             al(rrb_bytes);
-    double gb = 96.0;
-    {
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0)
-            gb = std::min(gb, 0.5 * (double)(free_b + c->d_wave.cap()) / 1073741824.0);
-    }
-    if (c->knobs.wave_buffer_gb > 0) gb = c->knobs.wave_buffer_gb;
-    int64_t batch = (int64_t)(gb * 1073741824.0) / per_tile;
-    if (batch < 1) batch = 1;
-    if (batch > rp.n_slots) batch = rp.n_slots > 0 ? rp.n_slots : 1;
-    const size_t need = (size_t)(batch * per_tile);
-    if (const int rc = c->d_wave.ensure(c, need)) return rc;
+    size_t free_b = 0, total_b = 0, hbm_free = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > 0) hbm_free = free_b + c->d_wave.cap();
+    const pbrtroute::WaveCarve wc = pbrtroute::wave_carve(c->knobs, c->facts, c->rp, kSizes, hbm_free);
+    if (const int rc = c->d_wave.ensure(c, wc.need)) return rc;
     WaveBufs& wb = c->wb;
     unsigned char* p = c->d_wave.get();
-    auto take = [&](int64_t bytes_per_tile) {
-        unsigned char* q = p;
-        p += batch * al(bytes_per_tile);
-        return q;
-    };
-    wb.prec = (PixelRec*)take(ppt * (int64_t)sizeof(PixelRec));
-    wb.s1d = (double*)take(ppt * nd * n * 8);
-    wb.memb = (uint64_t*)take(ppt * n * 8);
-    wb.L = (double*)take(ppt * n * 24);
-    wb.rays = (uint32_t*)take(ppt * n * 4);
-    wb.ppanic = (PanicRec*)take(ppt * (int64_t)sizeof(PanicRec));
-    wb.tile_npx = (int32_t*)take(4);
-    wb.rrb = rrb_bytes ? (RrBranches*)take(rrb_bytes) : nullptr;
-    wb.ppt = ppt;
-    wb.s1d_stride = nd * n;
-    c->wave_batch = batch;
+    wb.prec = (PixelRec*)(p + wc.prec);
+    wb.s1d = (double*)(p + wc.s1d);
+    wb.memb = (uint64_t*)(p + wc.memb);
+    wb.L = (double*)(p + wc.L);
+    wb.rays = (uint32_t*)(p + wc.rays);
+    wb.ppanic = (PanicRec*)(p + wc.ppanic);
+    wb.tile_npx = (int32_t*)(p + wc.tile_npx);
+    wb.rrb = wc.rrb >= 0 ? (RrBranches*)(p + wc.rrb) : nullptr;
+    wb.ppt = wc.ppt;
+    wb.s1d_stride = wc.s1d_stride;
+    c->wave_batch = wc.batch;
     return PBRT_OK;
 }
 
+// A frame's decisions, all of them frame_route.h's: check the desc, derive its parameters, upload
+// the light distribution, choose the route, lay out the chain kernels' LDS, size the buffers.
 int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
-    if (!rd) return set_err(c, PBRT_E_INVALID, "null render desc");
-    if (rd->tile_size <= 0 || rd->sampler_x <= 0 || rd->sampler_y <= 0 || rd->n_dims < 0 || rd->n_dims > 64)
-        return set_err(c, PBRT_E_INVALID, "bad sampler / tile size");
-    if ((int64_t)rd->sampler_x * rd->sampler_y > (1 << 20)) return set_err(c, PBRT_E_INVALID, "spp too large");
-    if (rd->integrator != PBRT_INTEGRATOR_PATH && rd->integrator != PBRT_INTEGRATOR_DIRECT_LIGHTING)
-        return set_err(c, PBRT_E_UNSUPPORTED, "unknown integrator");
-    if (rd->integrator == PBRT_INTEGRATOR_DIRECT_LIGHTING && rd->dl_strategy != PBRT_DL_UNIFORM_SAMPLE_ALL &&
-        rd->dl_strategy != PBRT_DL_UNIFORM_SAMPLE_ONE)
-        return set_err(c, PBRT_E_UNSUPPORTED, "unknown DirectLighting strategy");
-    if (rd->mode != PBRT_MODE_EXACT && rd->mode != PBRT_MODE_THROUGHPUT)
-        return set_err(c, PBRT_E_INVALID, "unknown mode");
+    using pbrtroute::Route;
     const pbrt_film_desc& f = c->host_scene.film;
-    if (f.filter_radius_x <= 0 || f.filter_radius_y <= 0 || f.filter_radius_x >= (double)rd->tile_size ||
-        f.filter_radius_y >= (double)rd->tile_size)
-        return set_err(c, PBRT_E_UNSUPPORTED, "filter radius must be in (0, tile_size)");
-    if ((rd->flags & PBRT_FLAG_PANIC_FIDELITY) && c->non_matte)
-        return set_err(c, PBRT_E_UNSUPPORTED, "panic fidelity covers Matte scenes only");
-    if (rd->integrator == PBRT_INTEGRATOR_DIRECT_LIGHTING && c->non_matte && rd->max_depth > 2 * kDlMaxLevels)
-        return set_err(c, PBRT_E_UNSUPPORTED, "DirectLighting through glass: maxDepth must be <= 64");
+    const pbrtroute::Refusal bad = pbrtroute::check_render(c->facts, f, rd);
+    if (bad.code != PBRT_OK) return set_err(c, bad.code, bad.text);
     RenderParams& rp = c->rp;
-    std::memset(&rp, 0, sizeof(rp));
-    rp.film_min_x = f.crop_min_x;
-    rp.film_min_y = f.crop_min_y;
-    rp.film_w = f.crop_max_x - f.crop_min_x;
-    rp.film_h = f.crop_max_y - f.crop_min_y;
-    rp.tile_size = rd->tile_size;
-    rp.ntx = (rp.film_w + rd->tile_size - 1) / rd->tile_size;
-    rp.nty = (rp.film_h + rd->tile_size - 1) / rd->tile_size;
-    int64_t total = rp.ntx * rp.nty;
-    int64_t begin = rd->tile_begin < 0 ? 0 : rd->tile_begin;
-    int64_t end = rd->tile_end > 0 && rd->tile_end < total ? rd->tile_end : total;
-    int64_t stride = rd->tile_stride > 0 ? rd->tile_stride : 1;
-    rp.tile_begin = begin;
-    rp.tile_stride = stride;
-    rp.n_slots = begin < end ? (end - begin + stride - 1) / stride : 0;
-    rp.slot_w = rd->tile_size + 2 * ((int64_t)f.filter_radius_x + 1);
-    rp.slot_h = rd->tile_size + 2 * ((int64_t)f.filter_radius_y + 1);
-    rp.xs = rd->sampler_x;
-    rp.ys = rd->sampler_y;
-    rp.spp = rd->sampler_x * rd->sampler_y;
-    rp.ndims = rd->n_dims;
-    rp.jitter = rd->jitter ? 1 : 0;
-    rp.integrator = rd->integrator;
-    rp.max_depth = rd->max_depth;
-    rp.dl_strategy = rd->dl_strategy;
-    rp.rr_threshold = rd->rr_threshold;
-    rp.lanes_per_wave = c->lanes_per_wave;
-    rp.flags = rd->flags;
-    rp.mode = rd->mode;
-    rp.ci_nps = 0;   // set per k_chain_ci launch (launch_ci)
-    rp.ci_scap = c->knobs.ci_scap;
+    rp = pbrtroute::render_params(c->facts, c->knobs, f, *rd, c->lanes_per_wave);
     pbrt_distribution_desc& dist = c->host_dist;
     std::memset(&dist, 0, sizeof(dist));
     if (rd->integrator == PBRT_INTEGRATOR_PATH) {
@@ -608,61 +266,20 @@ int prepare(pbrt_gpu_ctx* c, const pbrt_render_desc* rd) {
         if (rc != PBRT_OK) return set_err(c, rc, "unsupported light sample strategy");
         HIPCHK(c, hipMemcpyAsync(c->d_dist.get(), &dist, sizeof(dist), hipMemcpyHostToDevice, c->stream));
     }
-    {
-        const int64_t n = rp.spp, s1 = rp.jitter ? 2 * n : n, s2 = rp.jitter ? 3 * n : n;
-        const int64_t E = (int64_t)rp.ndims * (s1 + s2), V = E + 64 + E / 8;
-        rp.sp_events = (int32_t)E;
-        rp.sp_draws = (int32_t)V;
-        rp.sp_serial = V * 4 <= PBRT_SP_SERIAL_KB * 1024 ? 0 : 1;
-        // the windowed wave StartPixel where the serial one would run, without
-        // jitter (values are functions of their index), while its picks and
-        // permutations fit PBRT_SP_WINDOW_KB of LDS (config C; E's 1024 spp stay serial)
-        // (k_chain_ci instantiates it for Matte scenes of LDS-staged trees, the
-        // analytic walk: the host runs those kernels below)
-        rp.sp_window = c->knobs.sp_window && rp.sp_serial && !rp.jitter && !c->non_matte && c->host_scene.n_nodes <= kLdsNodes &&
-                       c->mesh.n_nodes == 0 &&
-                       (int64_t)rp.ndims * n * 4 + kSpRing * 4 <= PBRT_SP_WINDOW_KB * 1024 ? 1 : 0;
+    const pbrtroute::Routed r = pbrtroute::route(c->kernel_req, c->facts, c->knobs, *rd, rp, dist);
+    if (r.refusal.code != PBRT_OK) return set_err(c, r.refusal.code, r.refusal.text);
+    c->route = r.route;
+    c->mesh_only = pbrtroute::mesh_only(c->facts);
+    if (c->route == Route::Cam) {
+        c->lay.Lcam = pbrtroute::layout_Lcam(rp);
+    } else if (c->route != Route::Serial) {
+        c->lay.L = pbrtroute::layout_L(rp);
+        c->lay.Lci = pbrtroute::layout_Lci(rp);
+        c->tiles_per_wave = pbrtroute::tiles_per_wave(c->lanes_per_wave_set, c->lanes_per_wave);
     }
-    // the camera-start route is opt-in (AUTO keeps its renders on the serial kernel)
-    c->use_cam = false;
-    if (c->kernel_req == PBRT_KERNEL_WAVE_CAM) {
-        std::string why;
-        if (!wave_cam_eligible(c, rd, rp, c->lay_cam, why))
-            return set_err(c, PBRT_E_UNSUPPORTED, "render not eligible for the camera-start wave kernels: " + why);
-        c->use_cam = true;
-    }
-    c->use_spec = !c->use_cam && c->kernel_req != PBRT_KERNEL_SERIAL && wave_eligible(c, rd, rp, c->lay, c->lay_ci);
-    if ((c->kernel_req == PBRT_KERNEL_WAVE || c->kernel_req == PBRT_KERNEL_WAVEFRONT ||
-         c->kernel_req == PBRT_KERNEL_WAVE_CI) && !c->use_spec)
-        return set_err(c, PBRT_E_UNSUPPORTED, "render not eligible for the wave-parallel kernels");
-    c->use_dl = c->use_spec && rd->integrator == PBRT_INTEGRATOR_DIRECT_LIGHTING;
-    if (c->use_dl && c->kernel_req != PBRT_KERNEL_AUTO && c->kernel_req != PBRT_KERNEL_WAVE_DL)
-        return set_err(c, PBRT_E_UNSUPPORTED, "DirectLighting runs on the serial or the k_dl_* kernels");
-    if (!c->use_dl && c->kernel_req == PBRT_KERNEL_WAVE_DL)
-        return set_err(c, PBRT_E_UNSUPPORTED, "render not eligible for the DirectLighting wave kernels");
-    // the chain stage of the wave pipeline is k_chain_ci (PBRT_KERNEL_WAVE and
-    // _WAVEFRONT, whose window and wavefront chains it replaced, select it too)
-    c->use_ci = c->use_spec && !c->use_dl;
-    if (c->use_cam && rp.n_slots > 0) {
-        int rcw = wave_buffers(c);
-        if (rcw != PBRT_OK) return rcw;
-    }
-    if (c->use_spec && rp.n_slots > 0) {
-        int rcw = wave_buffers(c);
-        if (rcw != PBRT_OK) return rcw;
-        // tiles per k_chain_ci wave (opts.lanes_per_wave = 1, 2 or 4; default 1).
-        // One tile per wave is fastest on MI355X: its 64 trajectories leave the
-        // same bounce-1 point, so their traversals stay coherent; packing tiles
-        // cuts speculation but a window lasts as long as its slowest lane, and
-        // mixed-tile windows measured 2.5x slower per window.
-        int G = 1;
-        if (c->lanes_per_wave_set && c->lanes_per_wave >= 1 && c->lanes_per_wave <= kCiMaxGroups &&
-            (c->lanes_per_wave & (c->lanes_per_wave - 1)) == 0)
-            G = c->lanes_per_wave;
-        c->tiles_per_wave = G;
-    }
-    size_t nslot = (size_t)(rp.n_slots > 0 ? rp.n_slots : 1);
     int rc;
+    if (c->route != Route::Serial && rp.n_slots > 0 && (rc = wave_buffers(c)) != PBRT_OK) return rc;
+    size_t nslot = (size_t)(rp.n_slots > 0 ? rp.n_slots : 1);
     if ((rc = c->d_films.ensure(c, nslot * (size_t)(rp.slot_w * rp.slot_h * 3)))) return rc;
     if ((rc = c->d_s1d.ensure(c, nslot * (size_t)(rp.ndims > 0 ? rp.ndims : 1) * (size_t)rp.spp)))
         return rc;
@@ -707,9 +324,9 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, c->device) == hipSuccess && prop.multiProcessorCount > 0) {
-            c->dev.n_simd = 4 * prop.multiProcessorCount;
-            c->dev.lds_per_block = prop.sharedMemPerBlock;
-            if (prop.maxSharedMemoryPerMultiProcessor > 0) c->dev.lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
+            c->facts.n_simd = 4 * prop.multiProcessorCount;
+            c->facts.lds_per_block = prop.sharedMemPerBlock;
+            if (prop.maxSharedMemoryPerMultiProcessor > 0) c->facts.lds_per_cu = prop.maxSharedMemoryPerMultiProcessor;
         }
     }
     std::vector<uint32_t> order;
@@ -719,14 +336,7 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
     }
     c->host_scene = *scene;
     c->scene_hash = scene_content_hash(scene);
-    c->non_matte = false;
-    for (int i = 0; i < scene->n_materials; i++)   // Mirror, Glass or OrenNayar (Matte with sigma != 0)
-        c->non_matte |= scene->materials[i].type != PBRT_MAT_MATTE ||
-                        !(std::min(std::max(scene->materials[i].sigma, 0.0), 90.0) == 0);
-    c->rough_glass = false;
-    for (int i = 0; i < scene->n_materials; i++)
-        c->rough_glass |= scene->materials[i].type == PBRT_MAT_GLASS &&
-                          !(scene->materials[i].u_roughness == 0 && scene->materials[i].v_roughness == 0);
+    pbrtroute::scene_facts(*scene, c->facts);
     c->h_node_prims.resize((size_t)scene->n_nodes);
     for (int i = 0; i < scene->n_nodes; i++) c->h_node_prims[i] = scene->nodes[i].n_prims;
     c->host_scene.shapes = nullptr;
@@ -785,6 +395,7 @@ int pbrt_gpu_create(const pbrt_scene_desc* scene, const pbrt_gpu_opts* opts, pbr
         }
     }
     c->host_scene.meshes = nullptr;
+    c->facts.mesh = c->mesh.n_nodes != 0;
     *out = c;
     return PBRT_OK;
 }
@@ -809,11 +420,10 @@ namespace {
 // ---- The frame's stages, in the order render_enqueue runs them. Each is a plain
 // function over the context, the scene view and the batch.
 
-// Is the tree staged in LDS? (stage_nodes' own test.) A tree beyond kLdsNodes is walked with the
-// [64] stack: the k_*_cam_stack kernels and the kDepth = 64 chains. Those are compiled with
-// use_lds_nodes = 0 (no staged walk): select them by this test only, never for a tree the other
-// kernels would stage.
-bool tree_in_lds(const pbrt_gpu_ctx* c) { return c->host_scene.n_nodes <= kLdsNodes; }
+// A tree is staged in LDS while n_nodes <= kLdsNodes (stage_nodes' own test). Beyond, it is walked
+// with the [64] stack: the k_*_cam_stack kernels and the kDepth = 64 chains. Those are compiled
+// with use_lds_nodes = 0 (no staged walk): select them by this test only, never for a tree the
+// other kernels would stage.
 
 // The chain launch's schedule: workgroup b runs slot order[b] (null: launch order) and records its
 // chain time in ticks (null: not recorded). learned: the order comes from measured chain times.
@@ -851,7 +461,7 @@ int chain_schedule(pbrt_gpu_ctx* c, uint64_t key, int64_t nb, bool cache_heavy_k
     auto known = [&] { return c->sched.order_key == key && (int64_t)c->sched.h_slot_order.size() == nb; };
     bool cached = false;
     SchedEntry e;
-    if (!known() && ci_order_cache(c) && sched_cache_get(sched_cache_key(c, key), nb, e)) {
+    if (!known() && c->knobs.ci_order_cache && sched_cache_get(sched_cache_key(c, key), nb, e)) {
         c->sched.h_slot_order = std::move(e.order);
         if (cache_heavy_k) c->sched.heavy_k = e.heavy_k;
         c->sched.order_key = key;
@@ -881,7 +491,7 @@ int probe_order(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
         (rc = c->sched.d_cost_keys.ensure(c, (size_t)npad)))
         return rc;
     HIPCHK(c, hipMemsetAsync(c->sched.d_cost_keys.get(), 0xFF, sizeof(uint64_t) * (size_t)npad, c->stream));
-    launch_k(c, c->non_matte ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)b.nb), dim3(kWave), 0, c->stream,
+    launch_k(c, c->facts.non_matte ? k_tile_cost<true> : k_tile_cost<false>, dim3((unsigned)b.nb), dim3(kWave), 0, c->stream,
              with_slot(sc, 0), c->rp, c->wb, b.sb, b.nb, c->sched.d_cost.get(), c->sched.d_cost_keys.get());
     bitonic_sort_u64(c->sched.d_cost_keys.get(), (uint32_t)npad, c->stream, &c->log_frame);
     launch_k(c, k_order_of_keys, dim3((unsigned)((b.nb + 255) / 256)), dim3(256), 0, c->stream, c->sched.d_cost_keys.get(), b.nb,
@@ -896,7 +506,7 @@ int probe_order(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
 // k_film_cam's per-sample footprints; else k_film), then k_panic_reduce.
 void launch_films(pbrt_gpu_ctx* c, const Batch& b) {
     const RenderParams& rp = c->rp;
-    if (c->use_cam && rp.ndims == 0)
+    if (c->route == pbrtroute::Route::Cam && rp.ndims == 0)
         launch_k(c, rp.mode == PBRT_MODE_THROUGHPUT ? k_film_cam<true> : k_film_cam<false>, dim3((unsigned)b.nb),
                  dim3(kFilmThreads), 0, c->stream, c->d_film.get(), rp, c->wb, b.sb, b.nb, c->d_films.get(), c->cancel.d_seen.get(),
                  c->d_ctr.get());
@@ -916,8 +526,7 @@ void launch_films(pbrt_gpu_ctx* c, const Batch& b) {
 // is no bounce-1 record for k_tile_cost to probe from.
 int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
     const RenderParams& rp = c->rp;
-    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT, stack = !tree_in_lds(c);
-    c->last_kernel = PBRT_KERNEL_WAVE_CAM;
+    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT, stack = c->facts.n_nodes > kLdsNodes;
     int rc = ensure_batch_events(c);
     if (rc != PBRT_OK) return rc;
     c->ov.done = 0;
@@ -928,27 +537,25 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
         if (mb) {
             const int64_t blocks = rp.ndims > 0 ? nrec : (nrec + kWave - 1) / kWave;
-            launch_k(c, k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay_cam.staging, c->stream,
-                     with_slot(sc, 4), rp, c->lay_cam, c->d_jump.get(), c->wb, sb, nb);
+            launch_k(c, k_cam_setup, dim3((unsigned)blocks), dim3(kWave), (unsigned)c->lay.Lcam.staging, c->stream,
+                     with_slot(sc, 4), rp, c->lay.Lcam, c->d_jump.get(), c->wb, sb, nb);
         } else {
-            if (c->n_batches == 1 && ci_order_enabled(c)) {
+            if (c->n_batches == 1 && c->knobs.ci_order) {
                 // key -1: no k_chain_ci launch has this wave count. A cached entry's heavy count is the
                 // chain route's: there is no split here, every slot runs 1 wave at 3 waves/SIMD
-                if ((rc = chain_schedule(c, schedule_key(rp, -1), nb, false, b.sched)) != PBRT_OK) return rc;
+                if ((rc = chain_schedule(c, pbrtroute::schedule_key(rp, -1), nb, false, b.sched)) != PBRT_OK) return rc;
                 if (kTickPlanes > 1)  // diagnostics builds read start / end clocks this kernel does not record
                     HIPCHK(c, hipMemsetAsync(c->sched.d_ticks.get(), 0, sizeof(uint32_t) * (size_t)nb * kTickPlanes, c->stream));
                 c->sched.h_slot_kw.assign((size_t)nb, (uint8_t)1);
                 c->sched.ci_wps = 3;
             }
             launch_k(c, stack ? k_chain_cam_stack : k_chain_cam, dim3((unsigned)nb), dim3(kWave),
-                     (unsigned)c->lay_cam.total, c->stream, with_slot(sc, 2), rp, c->lay_cam, c->d_jump.get(), c->wb, sb, nb,
+                     (unsigned)c->lay.Lcam.total, c->stream, with_slot(sc, 2), rp, c->lay.Lcam, c->d_jump.get(), c->wb, sb, nb,
                      b.sched.order, b.sched.ticks);
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
         if (rp.spp > 1) {
-            // pixels per wave: about 256 (pixel, sample) work items, so that the lanes stay
-            // filled at a few samples per pixel too
-            const int m = rp.spp - 1, pp = m >= 32 ? 4 : m >= 8 ? 16 : 64;
+            const int pp = pbrtroute::cam_pixels_per_wave(rp.spp);
             const PathsCamKernel kern = paths_cam_kernel(pp, mb, stack);
             if (!kern) return set_err(c, PBRT_E_HIP, "no k_paths_cam instantiation for P = " + std::to_string(pp));
             launch_k(c, kern, dim3((unsigned)((nrec + pp - 1) / pp)), dim3(kWave), 0, c->stream,
@@ -962,15 +569,15 @@ int enqueue_cam(pbrt_gpu_ctx* c, const DevScene& sc) {
 
 // k_wf_primary: bounce 1 of every pixel of the batch.
 void launch_primary(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
-    launch_k(c, c->non_matte ? k_wf_primary<true> : k_wf_primary<false>,
+    launch_k(c, c->facts.non_matte ? k_wf_primary<true> : k_wf_primary<false>,
              dim3((unsigned)((b.nb * c->wb.ppt + kWave - 1) / kWave)), dim3(kWave), 0, c->stream, with_slot(sc, 1),
              c->rp, c->wb, b.sb, b.nb);
 }
 
 // THROUGHPUT: k_mb_setup (StartPixel + bounce 1 per pixel) instead of the chain.
 void launch_mb_setup(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
-    launch_k(c, c->non_matte ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(b.nb * c->wb.ppt)), dim3(kWave),
-             (unsigned)c->lay.total, c->stream, with_slot(sc, 4), c->rp, c->lay, c->d_jump.get(), c->wb, b.sb, b.nb);
+    launch_k(c, c->facts.non_matte ? k_mb_setup<true> : k_mb_setup<false>, dim3((unsigned)(b.nb * c->wb.ppt)), dim3(kWave),
+             (unsigned)c->lay.L.total, c->stream, with_slot(sc, 4), c->rp, c->lay.L, c->d_jump.get(), c->wb, b.sb, b.nb);
 }
 
 // k_paths_ci (lane-refill paths) over n slots of the batch on stream st; ord: the slots' order,
@@ -978,15 +585,14 @@ void launch_mb_setup(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
 int launch_paths(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, bool mb, const uint32_t* ord, int64_t n,
                  hipStream_t st) {
     const RenderParams& rp = c->rp;
-    const int pp = paths_ci_pixels(c, rp);
-    const int sl = paths_ci_s1d_lds(c, rp, pp) ? 1 : 0;
-    const PathsCiKernel kern = paths_ci_kernel(pp, mb, c->non_matte);
+    const int pp = pbrtroute::paths_ci_pixels(c->knobs, c->facts);
+    const int sl = pbrtroute::paths_ci_s1d_lds(c->knobs, rp, pp) ? 1 : 0;
+    const PathsCiKernel kern = paths_ci_kernel(pp, mb, c->facts.non_matte);
     const int lds = paths_ci_lds(pp, sl * rp.ndims * rp.spp);
     if (!kern || lds < 0)
         return set_err(c, PBRT_E_HIP, "no k_paths_ci instantiation for P = " + std::to_string(pp) +
-                                          (c->non_matte ? ", kX" : ""));
-    // ordered: whole slots, ceil(ppt / pp) workgroups each (pp need not divide ppt)
-    const int64_t groups = ord ? n * ((c->wb.ppt + pp - 1) / pp) : (n * c->wb.ppt + pp - 1) / pp;
+                                          (c->facts.non_matte ? ", kX" : ""));
+    const int64_t groups = pbrtroute::paths_ci_groups(c->wb.ppt, pp, n, ord != nullptr);
     launch_k(c, kern, dim3((unsigned)groups), dim3(kWave), (unsigned)lds, st, with_slot(sc, mb ? 5 : 3), rp, c->wb,
              b.sb, n * c->wb.ppt, c->d_ctr.get(), sl, ord);
     return PBRT_OK;
@@ -994,100 +600,28 @@ int launch_paths(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, bool mb, c
 
 // One k_chain_ci launch of n workgroups at w waves per tile on stream st, workgroup i on slot
 // ord[i] (identity if null); prog: the completion record of the overlapped path stage, or null.
-// nps_allowed: the caller's leave for next-pixel speculation (k_chain_ci kNps: Matte, stride 1),
-// which only launches of multi-wave tiles use. The heavy launch of a split does without it unless
-// its light tiles are multi-wave too: its two rings' LDS cost the light tiles beside it (1/4 shard
-// of B 132 -> 145 ms; a 1/8 shard, no split: 131.5 -> 127.2 ms).
-// Sets c->sched.ci_wps for a one-wave launch (pbrt_gpu_synchronize's heavy threshold reads it).
+// nps_allowed: the caller's leave for next-pixel speculation. pbrtroute::chain_launch chooses the
+// instantiation and its numbers. Sets c->sched.ci_wps for a one-wave launch (pbrt_gpu_synchronize's
+// heavy threshold reads it).
 int launch_ci(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, int w, int64_t n, const uint32_t* ord,
               hipStream_t st, uint32_t* prog, bool nps_allowed) {
-    const bool kx = c->non_matte, mesh_only = mesh_only_scene(c), lds_nodes = tree_in_lds(c);
+    const pbrtroute::ChainLaunch l =
+        pbrtroute::chain_launch(c->knobs, c->facts, c->rp, c->lay.Lci, kSizes, c->tiles_per_wave, c->mesh_only, w, n,
+                                nps_allowed, [c](bool multi) { return ci_static_lds(c, multi); });
     RenderParams rpl = c->rp;
-    int Gc = 1, eu = 0;   // tiles per wave; waves/SIMD the build's registers are budgeted for (0: 3)
-    unsigned lds = 0;
-    ChainLayout lw;
-    if (w > 1) {   // one tile per workgroup of w waves; the ring grows with the lanes
-        rpl.ci_nps = (!kx && nps_allowed && ci_stride(c, w) == 1) ? c->knobs.ci_nps : 0;
-        lw = ci_layout(c->lay_ci, w, 1, lds, rpl.ci_nps > 0);
-    } else {
-        Gc = std::min(c->tiles_per_wave, kCiMaxGroups);
-        lw = ci_layout(c->lay_ci, 1, Gc, lds);
-        // Matte analytic scenes: the 3-waves/SIMD build unless the workgroup's LDS (large spp:
-        // StartPixel staging) caps the CU below 3 waves/SIMD, where the 2-wave build (no spills)
-        // is faster (config C: 6.53 vs 7.41 s). kX and mesh chains have no 2-wave build.
-        const bool eu2 = !kx && !mesh_only &&
-                         (c->knobs.ci_eu == 2 || (c->knobs.ci_eu != 3 && !ci_eu3_fits(c, lds, lds_nodes, Gc > 1)));
-        eu = eu2 ? 2 : 0;
-        c->sched.ci_wps = (kx || eu2) ? 2 : 3;
-    }
-    // The instantiation, stated once. Walk: a mesh-only scene has no analytic one (-1), else the
-    // staged tree (0) or the [64] stack (64). rp.sp_window is set for Matte scenes of staged trees
-    // only (prepare). One wave per tile keeps the group's state in scalar registers; several tiles
-    // per wave (opts.lanes_per_wave) run the per-lane kMulti code, and so does the one-wave kX chain
-    // (lanes_per_tile = 64): with the scalar state config G measured 473.5 against 471.5 ms
-    // (profiles/chain_sgpr/), so kX has no other one-wave instantiation. kX runs at most 4 waves
-    // per tile (ci_waves, ci_heavy_waves).
-    const int depth = mesh_only ? -1 : lds_nodes ? 0 : 64;
-    const bool multi = w == 1 && (kx || Gc > 1);
-    const ChainKernel kern = chain_kernel(w, depth, kx, eu, c->rp.sp_window != 0, multi);
+    rpl.ci_nps = l.nps;
+    if (l.ci_wps) c->sched.ci_wps = l.ci_wps;
+    const ChainKernel kern = chain_kernel(l.w, l.depth, l.kx, l.eu, l.window, l.multi);
     if (!kern)
         return set_err(c, PBRT_E_HIP, "no k_chain_ci instantiation for " + std::to_string(w) + " waves, walk " +
-                                          std::to_string(depth) + (kx ? ", kX" : "") + (multi ? ", multi" : ""));
-    const int ring = w * kCiRingBytes / (int)sizeof(RingEnt) / Gc;
-    const bool per_tile = Gc == 1;   // the order and the clocks need one tile per workgroup
-    launch_k(c, kern, dim3((unsigned)((n + Gc - 1) / Gc)), dim3(kWave * w), lds, st, with_slot(sc, 2), rpl, lw,
-             c->d_jump.get(), c->wb, b.sb, b.nb, kWave * w / Gc, ring, c->d_ctr.get(), per_tile ? ord : nullptr,
-             per_tile ? b.sched.ticks : nullptr, ci_stride(c, w), prog);
+                                          std::to_string(l.depth) + (l.kx ? ", kX" : "") + (l.multi ? ", multi" : ""));
+    launch_k(c, kern, dim3(l.grid), dim3(l.block), l.lds, st, with_slot(sc, 2), rpl, l.lay, c->d_jump.get(), c->wb, b.sb,
+             b.nb, l.lanes_per_tile, l.ring, c->d_ctr.get(), l.per_tile ? ord : nullptr,
+             l.per_tile ? b.sched.ticks : nullptr, l.stride, prog);
     return PBRT_OK;
 }
 
-// The heavy/light split of a k_chain_ci stage: the `heavy` slots at the front of the order run
-// heavy_w waves each in a launch of their own, the rest light_w (0: one launch at kw).
-struct Split {
-    int64_t heavy;
-    int heavy_w, light_w;
-    bool light_kw;   // the light tiles are multi-wave too: both launches keep next-pixel speculation
-};
-// the heaviest tiles of the last frame get 4 waves each; they are launched first, on the main
-// stream, and the rest concurrently on another (same-stream launches would serialise)
-// (multi-GPU shards, where kw > 1: the rest then run at 1 wave per tile, the most efficient per
-// lane; PBRT_CI_LIGHT_KW=1: at kw)
-Split ci_split(const pbrt_gpu_ctx* c, int64_t nb, int kw, bool learned, int G, bool kx, bool mesh_only) {
-    Split s{};
-    s.light_kw = kw > 1 && c->knobs.ci_light_kw;
-    s.light_w = s.light_kw ? kw : 1;
-    s.heavy_w = ci_heavy_waves(c);
-    // measured wins at 1/2 and 1/4 shards (nb > n_simd); a loss at 1/8
-    // (1020 tiles: 294 -> 307 ms), so smaller launches never split
-    // one GPU (kw == 1): since the Matte chain runs 3 waves/SIMD the whole
-    // frame's lane time is below its heaviest tile's chain, so the heaviest
-    // tiles get 4 waves there too (config B: chain 328.5 -> 313.3 ms)
-    // (measured a loss on the mesh chain, D 825 -> 920 ms, and on kX, G 509 -> 517 ms:
-    // one GPU splits only the 3-wave Matte analytic chain)
-    bool split1 = false;
-    if (kw == 1 && G == 1 && !kx && !mesh_only) {
-        unsigned lds1 = 0;
-        (void)ci_layout(c->lay_ci, 1, 1, lds1);
-        split1 = ci_eu3_fits(c, lds1, tree_in_lds(c));
-    }
-    if (learned && G == 1 && (kw > 1 ? nb > c->dev.n_simd : split1) && ci_split_enabled(c))
-        s.heavy = std::min<int64_t>(c->sched.heavy_k, nb);
-    if (ci_heavy_override(c) >= 0 && learned && G == 1)   // tests and experiments force the split
-        s.heavy = std::min<int64_t>(ci_heavy_override(c), nb);
-    // a multi-wave Matte shard that fits the wave slots (1/8 of B: 1020 tiles at 4 waves)
-    // is bound by its heaviest tiles' pixel-serial chains: those at 8 waves, the
-    // rest at kw, next-pixel speculation in both (the N=8 shards' max 121.9 ->
-    // ~107 ms with 32; 4-32 within a few ms; all tiles at 8 waves: 178 ms)
-    if (s.heavy == 0 && ci_heavy_override(c) < 0 && learned && G == 1 && kw > 1 && nb <= c->dev.n_simd && !kx &&
-        !mesh_only && ci_split_enabled(c) && c->knobs.ci_split8 > 0) {
-        s.heavy = std::min<int64_t>(c->knobs.ci_split8, nb / 16);
-        s.light_kw = true;
-        s.light_w = kw;
-        s.heavy_w = 8;
-    }
-    if (s.heavy >= nb) s.heavy = 0;   // nothing left for the light launch: one launch at kw
-    return s;
-}
+using pbrtroute::Split;
 
 // PBRT_PATHS_OVERLAP (a learned frame, one tile per workgroup): the completion-driven path stage.
 //  - the heavy launch on the main stream (normal priority);
@@ -1123,7 +657,7 @@ int overlap_arm(pbrt_gpu_ctx* c, int64_t nb) {
 int launch_path_chunks(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_split, 0));
     for (int64_t s0 = 0, j = 0; s0 < b.nb; j++) {
-        const int64_t e0 = j + 1 >= c->knobs.paths_overlap ? b.nb : s0 + std::max<int64_t>(1, (b.nb - s0) / 2);
+        const int64_t e0 = pbrtroute::path_chunk_end(b.nb, s0, j, c->knobs.paths_overlap);
         launch_k(c, k_gate, dim3(1), dim3(kWave), 0, c->stream2, c->ov.d_prog.get(), (uint32_t)s0, (uint32_t)e0, c->d_ctr.get());
         const int rc = launch_paths(c, sc, b, false, c->ov.d_prog.get() + kProgHead + s0, e0 - s0, c->stream2);
         if (rc != PBRT_OK) return rc;
@@ -1190,30 +724,29 @@ int chain_unsplit_overlap(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b, i
 int chain_stage(pbrt_gpu_ctx* c, const DevScene& sc, Batch& b) {
     const RenderParams& rp = c->rp;
     const int G = c->tiles_per_wave;
-    const bool kx = c->non_matte;   // Mirror / smooth Glass / OrenNayar: the kX instantiations
-    const bool mesh_only = mesh_only_scene(c);   // triangle meshes and nothing else: no analytic walk
     Schedule& s = b.sched;
     int rc;
     launch_primary(c, sc, b);
-    const int kw = ci_waves(c, b.nb);
-    if ((kw > 1 || G == 1) && c->n_batches == 1 && ci_order_enabled(c)) {
+    const int kw = pbrtroute::ci_waves(c->knobs, c->facts, G, b.nb);
+    if ((kw > 1 || G == 1) && c->n_batches == 1 && c->knobs.ci_order) {
         // keyed by the waves per tile; a cached entry brings its heavy count; a frame without a
         // measured order runs the cold-frame probe
-        if ((rc = chain_schedule(c, schedule_key(rp, kw), b.nb, true, s)) != PBRT_OK) return rc;
+        if ((rc = chain_schedule(c, pbrtroute::schedule_key(rp, kw), b.nb, true, s)) != PBRT_OK) return rc;
         c->sched.probed = false;
-        if (!s.order && ci_probe_enabled(c) && b.nb <= (int64_t)1 << 24) {
+        if (!s.order && c->knobs.ci_probe && b.nb <= (int64_t)1 << 24) {
             if ((rc = probe_order(c, sc, b)) != PBRT_OK) return rc;
             s.order = c->sched.d_slot_order.get();
         }
     }
-    const Split sp = ci_split(c, b.nb, kw, s.learned, G, kx, mesh_only);
+    const Split sp = pbrtroute::ci_split(c->knobs, c->facts, c->lay.Lci, kSizes, c->mesh_only, b.nb, kw, s.learned, G,
+                                         c->sched.heavy_k, [c](bool multi) { return ci_static_lds(c, multi); });
     c->sched.last_heavy = sp.heavy;
     if (s.ticks) {   // label every slot with the waves it actually runs at
         c->sched.h_slot_kw.assign((size_t)b.nb, (uint8_t)(sp.heavy > 0 ? sp.light_w : kw));
         for (int64_t i = 0; i < sp.heavy; i++) c->sched.h_slot_kw[c->sched.h_slot_order[(size_t)i]] = (uint8_t)sp.heavy_w;
     }
     // the completion-driven path stage takes EXACT k_paths_ci (path_stage's last case) and a learned order
-    const bool paths_ci_exact = !(paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0);
+    const bool paths_ci_exact = !pbrtroute::paths_on_wavefront(c->knobs, c->facts);
     const bool ov_ok = c->knobs.paths_overlap > 0 && paths_ci_exact && s.learned && !c->ov.retry && c->ov.stalls < 2;
     const bool overlap = sp.heavy > 0 && ov_ok;
     // no split: the completion list needs one tile per workgroup
@@ -1228,20 +761,18 @@ int chain_stage(pbrt_gpu_ctx* c, const DevScene& sc, Batch& b) {
 // The path stage of a batch, after its chain stage.
 int path_stage(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
     const RenderParams& rp = c->rp;
-    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
-    if (c->use_dl) {
+    const bool mb = c->route == pbrtroute::Route::Throughput;
+    if (c->route == pbrtroute::Route::DirectLighting) {
         const int64_t nrec = b.nb * c->wb.ppt;
         if (rp.spp > 1)
-            launch_k(c, c->non_matte ? k_dl_samples<true> : k_dl_samples<false>,
-                     dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave, (int64_t)c->dev.n_simd * 64)),
+            launch_k(c, c->facts.non_matte ? k_dl_samples<true> : k_dl_samples<false>,
+                     dim3((unsigned)std::min<int64_t>((nrec * (rp.spp - 1) + kWave - 1) / kWave, (int64_t)c->facts.n_simd * 64)),
                      dim3(kWave), 0, c->stream, with_slot(sc, 3), rp, c->wb, b.sb, nrec);
         launch_k(c, k_dl_panics, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, c->stream, rp, c->wb, b.sb, nrec,
                  c->d_ctr.get());
         return PBRT_OK;
     }
-    if (paths_wf_enabled(c) || paths_ci_pixels(c, rp) == 0) {
-        // the path wavefront: mesh scenes, and whatever k_paths_ci cannot
-        // take (a tree beyond LDS, more than 64 / P lights)
+    if (pbrtroute::paths_on_wavefront(c->knobs, c->facts)) {
         if (mb) launch_mb_setup(c, sc, b);
         return paths_wavefront(c, with_slot(sc, mb ? 5 : 3), b.sb, b.nb);
     }
@@ -1259,22 +790,21 @@ int path_stage(pbrt_gpu_ctx* c, const DevScene& sc, const Batch& b) {
 // The wave pipeline (DirectLighting, THROUGHPUT, EXACT Path on k_chain_ci), per batch: the chain
 // stage, the path stage, the tile films.
 int enqueue_wave(pbrt_gpu_ctx* c, const DevScene& sc) {
+    using pbrtroute::Route;
     const RenderParams& rp = c->rp;
-    const bool mb = rp.mode == PBRT_MODE_THROUGHPUT;
-    c->last_kernel = c->use_dl ? PBRT_KERNEL_WAVE_DL : mb ? PBRT_KERNEL_WAVE : PBRT_KERNEL_WAVE_CI;
     int rc = ensure_batch_events(c);
     if (rc != PBRT_OK) return rc;
     for (int64_t sb = 0, bi = 0; sb < rp.n_slots; sb += c->wave_batch, bi++) {
         Batch b{bi, sb, std::min<int64_t>(c->wave_batch, rp.n_slots - sb)};
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 0], c->stream));
         c->ov.done = 0;
-        if (c->use_dl) {
+        if (c->route == Route::DirectLighting) {
             launch_primary(c, sc, b);
             unsigned lds = 0;
-            const ChainLayout lw = ci_layout(c->lay_ci, 1, 1, lds);
+            const ChainLayout lw = pbrtroute::ci_layout(c->lay.Lci, 1, 1, lds, kSizes.chain_cache);
             launch_k(c, k_dl_setup, dim3((unsigned)b.nb), dim3(kWave), lds, c->stream, sc, rp, lw, c->d_jump.get(), c->wb,
                      sb, b.nb);
-        } else if (!mb) {   // (THROUGHPUT has no offset chain: every sample's stream is known up front)
+        } else if (c->route == Route::Chain) {   // (THROUGHPUT has no offset chain: every sample's stream is known up front)
             if ((rc = chain_stage(c, sc, b)) != PBRT_OK) return rc;
         }
         HIPCHK(c, hipEventRecord(c->bev[3 * bi + 1], c->stream));
@@ -1307,10 +837,10 @@ int render_enqueue(pbrt_gpu_ctx* c, const pbrt_render_desc* rd, double* film_dev
     HIPCHK(c, hipEventRecord(c->ev0, c->stream));
     if (rp.n_slots > 0) {
         DevScene sc = dev_scene(c, rd->integrator == PBRT_INTEGRATOR_PATH);
-        if (c->use_cam || c->use_spec) {
-            if ((rc = c->use_cam ? enqueue_cam(c, sc) : enqueue_wave(c, sc)) != PBRT_OK) return rc;
+        c->last_kernel = pbrtroute::last_kernel(c->route);
+        if (c->route != pbrtroute::Route::Serial) {
+            if ((rc = c->route == pbrtroute::Route::Cam ? enqueue_cam(c, sc) : enqueue_wave(c, sc)) != PBRT_OK) return rc;
         } else {
-            c->last_kernel = PBRT_KERNEL_SERIAL;
             c->n_batches = 0;
             const int64_t blocks = (rp.n_slots + rp.lanes_per_wave - 1) / rp.lanes_per_wave;
             const SerialKernel kern = serial_kernel(c->min_waves);
@@ -1405,10 +935,10 @@ int pbrt_gpu_synchronize(pbrt_gpu_ctx* c, pbrt_gpu_stats* stats) {
             HIPCHK(c, hipMemcpy(c->sched.h_tick_clocks.data(), c->sched.d_ticks.get() + t.size(), sizeof(uint32_t) * 2 * t.size(),
                                 hipMemcpyDeviceToHost));
         }
-        c->sched.heavy_k = learn_order(t, c->sched.h_slot_kw, c->sched.ci_wps, c->dev.n_simd, ci_heavy_override(c),
+        c->sched.heavy_k = learn_order(t, c->sched.h_slot_kw, c->sched.ci_wps, c->facts.n_simd, c->knobs.ci_heavy,
                                        c->sched.h_slot_order);   // schedule.h
         c->sched.order_key = c->sched.ticks_key;
-        if (ci_order_cache(c)) sched_cache_put(sched_cache_key(c, c->sched.ticks_key), c->sched.h_slot_order, c->sched.heavy_k);
+        if (c->knobs.ci_order_cache) sched_cache_put(sched_cache_key(c, c->sched.ticks_key), c->sched.h_slot_order, c->sched.heavy_k);
     }
     if (ctr.any_panic) {
         std::vector<PanicRec> pr((size_t)c->rp.n_slots);

@@ -8,10 +8,11 @@ tests/test_kernel_manifest.py (no GPU) holds COVERAGE + EXEMPT equal to the
 manifest; tests/test_gpu_kernel_coverage.py renders every case twice against
 the oracle and finds the kernels in the launch log.
 
-The launch decision each case steers is render.hip's: the arguments launch_ci,
-launch_paths, enqueue_cam and the serial launch give their kernel selectors
-(chain_kernel, paths_ci_kernel, paths_cam_kernel, serial_kernel), and
-paths_wavefront; the comment of a case says which condition selects its kernel.
+The launch decision each case steers is frame_route.h's (chain_launch, paths_ci_pixels,
+cam_pixels_per_wave, the route): the arguments render.hip's launch_ci, launch_paths,
+enqueue_cam and the serial launch give their kernel selectors (chain_kernel,
+paths_ci_kernel, paths_cam_kernel, serial_kernel), and paths_wavefront; the comment
+of a case says which condition selects its kernel.
 """
 from collections import namedtuple
 
@@ -84,7 +85,7 @@ CASES = {
     "spwin_w2": Case("readme16x16", SPWIN, {}, waves(2), CI, (ci(2, spwin=True),)),
     "spwin_w4": Case("readme16x16", SPWIN, {}, waves(4), CI, (ci(4, spwin=True),)),
     "spwin_w8": Case("readme16x16", SPWIN, {}, waves(8), CI, (ci(8, spwin=True),)),
-    # ---- mesh_only_scene: n_prims == 0; its paths run the kMeshOnly wavefront kernels
+    # ---- mesh_only: n_prims == 0; its paths run the kMeshOnly wavefront kernels
     "mesh_w1": Case("mesh48x32", S22, {}, waves(1), CI, (ci(1, -1), "k_pw_trace<true>", "k_pw_shadow<true>")),
     "mesh_w2": Case("mesh48x32", S22, {}, waves(2), CI, (ci(2, -1),)),
     "mesh_w4": Case("mesh48x32", S22, {}, waves(4), CI, (ci(4, -1),)),

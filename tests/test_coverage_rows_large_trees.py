@@ -27,11 +27,11 @@ SCENES = {
 }
 WAVE_CAM = dict(kernel="wave_cam")
 CASES = {
-    # non_matte and n_nodes > kLdsNodes: the kX chain with the [64] stack (launch_ci: kx, depth 64)
+    # non_matte and n_nodes > kLdsNodes: the kX chain with the [64] stack (chain_launch: kx, depth 64)
     "kx_stack_w1": Case("crowd48x32", S22, {}, waves(1), CI, (ci(1, 64, kx=True, multi=True),)),
     "kx_stack_w2": Case("crowd48x32", S22, {}, waves(2), CI, (ci(2, 64, kx=True),)),
     "kx_stack_w4": Case("crowd48x32", S22, {}, waves(4), CI, (ci(4, 64, kx=True),)),
-    # the camera-start route, n_nodes > kLdsNodes (enqueue_cam: !tree_in_lds); pixels per k_paths_cam_stack
+    # the camera-start route, n_nodes > kLdsNodes (enqueue_cam: n_nodes > kLdsNodes); pixels per k_paths_cam_stack
     # wave by spp - 1 (< 8: 64, < 32: 16, else 4)
     "cam_stack_p64": Case("crowd_matte48x32", dict(S22, **NOSAMP), WAVE_CAM, {}, CAM,
                           ("k_chain_cam_stack", "k_paths_cam_stack<64, false>")),

@@ -110,7 +110,7 @@ def check_two_frames(scene_key, lanes_per_wave=0, expect=None, **rd_kw):
 
 
 def chain_of(scene_key, waves, **kw):
-    """The instantiation a scene's class and PBRT_CI_WAVES select (render.hip launch_ci): the
+    """The instantiation a scene's class and PBRT_CI_WAVES select (frame_route.h chain_launch): the
     mesh-only walk, the [64]-stack walk beyond 64 nodes, kX; at one wave the register build
     is ci_eu3_fits' choice unless PBRT_CI_EU sets it."""
     w = int(waves)

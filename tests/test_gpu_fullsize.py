@@ -64,7 +64,7 @@ def test_config_B_whole_frame_vs_oracle():
     """The cold frame of a fresh context (probe order) and the steady-state
     frames the bench times: from the second frame on, the learned LPT order and
     the one-GPU heavy/light split (the heaviest tiles at 4 waves on one stream
-    beside the rest at 1 wave, render.hip launch_ci), with the path stage of the
+    beside the rest at 1 wave, frame_route.h ci_split and chain_launch), with the path stage of the
     heavy tiles and the light launch's first round overlapping the rest of the
     chain (PBRT_PATHS_OVERLAP, default on). Every frame is the oracle's, bit
     for bit."""

@@ -52,7 +52,7 @@ CASES = [(12, 12, 4, False), (16, 16, 4, False), (16, 16, 2, False), (16, 16, 1,
 
 
 def windowed(sx, sy, nd, jit):
-    """render.hip prepare(): rp.sp_window. The windowed StartPixel replaces the serial one
+    """frame_route.h render_params(): rp.sp_window. The windowed StartPixel replaces the serial one
     (raw draws V * 4 bytes beyond PBRT_SP_SERIAL_KB = 4 KB; V = E + 64 + E / 8 over E = n_dims *
     (2 n) events without jitter) where there is no jitter and the picks, permutations and the
     256-entry draw ring (n_dims * n * 4 + 1024 bytes) fit PBRT_SP_WINDOW_KB = 6 KB."""

@@ -46,7 +46,8 @@ def test_scene_tables_schedule_and_knobs(tmp_path):
 
 
 def test_the_host_headers_include_no_hip():
-    """knobs.h, scene_tables.h, schedule.h and bvh_tables.h take the public headers and the standard library only."""
+    """knobs.h, scene_tables.h, schedule.h and bvh_tables.h take the public headers and the standard library only;
+    render_params.h and frame_route.h besides those only each other and the headers above."""
     csrc = os.path.join(REPO, "go-pbrt_amd", "csrc")
     allowed = {"../../include/pbrt_gpu.h", "../../include/pbrt_scene.h", "../../include/pbrt_diag.h", "bvh_tables.h"}
     for name in ("knobs.h", "scene_tables.h", "schedule.h", "bvh_tables.h"):
@@ -56,3 +57,12 @@ def test_the_host_headers_include_no_hip():
                 assert inc.startswith("<") and "hip" not in inc or inc.strip('"') in allowed, (name, line)
     inc = [ln.split()[1] for ln in open(os.path.join(csrc, "bvh_tables.h")) if ln.startswith("#include")]
     assert inc == ["<cstdint>"]
+    # render_params.h (host and device): the standard library alone; frame_route.h: besides the public
+    # headers, knobs.h, bvh_tables.h and render_params.h
+    inc = [ln.split()[1] for ln in open(os.path.join(csrc, "render_params.h")) if ln.startswith("#include")]
+    assert inc == ["<cstdint>"]
+    allowed = {"../../include/pbrt_gpu.h", "../../include/pbrt_scene.h", "knobs.h", "bvh_tables.h", "render_params.h"}
+    for line in open(os.path.join(csrc, "frame_route.h")):
+        if line.startswith("#include"):
+            inc = line.split()[1]
+            assert inc.startswith("<") and "hip" not in inc or inc.strip('"') in allowed, line

@@ -64,6 +64,11 @@ def cases():
     readme64 = lambda: G.Scene.readme(64, 64)   # 16 tiles at 2 waves each: a shard that fits the wave slots
     out["shard_w2_split8"] = (readme64, abi.render_desc(2, 2), {}, {"PBRT_CI_WAVES": "2"})
     out["shard_w2_split8_off"] = (readme64, abi.render_desc(2, 2), {}, {"PBRT_CI_WAVES": "2", "PBRT_CI_SPLIT8": "0"})
+    # the one-wave Matte chain's build left to its rule (no PBRT_CI_EU): 256 spp (config C's sampler: the
+    # windowed StartPixel's staging still leaves 12 workgroups on a CU) and a tree beyond LDS (whose
+    # static LDS does not)
+    out["spp256_w1"] = (K.SCENES["readme16x16"], abi.render_desc(16, 16, max_depth=3), {}, {"PBRT_CI_WAVES": "1"})
+    out["stack_w1_auto"] = (K.SCENES["spheres90"], abi.render_desc(2, 2), {}, {"PBRT_CI_WAVES": "1"})
     two_tiles = lambda: G.Scene.readme(32, 16)
     out["batches_chain"] = (two_tiles, abi.render_desc(2, 2), {}, SMALL_BUFFER)
     out["batches_cam"] = (two_tiles, abi.render_desc(**dict(K.S22, **K.NOSAMP)), cam, SMALL_BUFFER)
