@@ -31,6 +31,7 @@ __device__ __forceinline__ void add_L(PathStateTap& s, Spec v) {
     s.flags |= kTapAdded;
 }
 __device__ __forceinline__ void add_rays(PathStateTap& s, uint32_t v) { s.rays += v; }
+__device__ __forceinline__ constexpr bool caller_eta(const PathStateTap&) { return true; }   // pbrt_path_soa's eta_scale
 __device__ __forceinline__ void note_hit(PathStateTap& s, const DevScene& sc, const SI& si) {
     s.flags |= kTapHit;
     const pbrt_hit_soa& h = s.step->hit;

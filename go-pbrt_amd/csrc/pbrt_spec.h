@@ -206,6 +206,12 @@ __device__ __forceinline__ void add_rays(PathStateLds& s, uint32_t v) { *s.rays 
 // another unit that surfaces the interaction has its own (k_path_step.hip).
 __device__ __forceinline__ void note_hit(PathState&, const DevScene&, const SI&) {}
 __device__ __forceinline__ void note_hit(PathStateLds&, const DevScene&, const SI&) {}
+// caller_eta: whether the state's eta_scale is a caller's (k_path_step.hip), so that Russian
+// roulette must read it on a Matte-only scene too (path.go:145-146: rrBeta = beta * etaScale). The two
+// states above start every path themselves: without a specular transmission (kX) etaScale is 1,
+// beta * 1 is beta, and no code is generated for the product.
+__device__ __forceinline__ constexpr bool caller_eta(const PathState&) { return false; }
+__device__ __forceinline__ constexpr bool caller_eta(const PathStateLds&) { return false; }
 // path_step's Cache of a kernel that runs path_step<2> only (k_paths_cam, k_li,
 // k_path_step): the bounce-1 cache is never read, and no code is generated for it.
 struct NoCache {
@@ -341,7 +347,7 @@ __device__ __forceinline__ bool path_step(const DevScene& sc, const Cache& pc, c
             s.ray.d = wi;
             s.ray.tmax = kInf;
             s.ray.time = isect.time;
-            Spec rr = smuls(s.beta, kX ? s.eta_scale : 1.0);
+            Spec rr = smuls(s.beta, (kX || caller_eta(s)) ? s.eta_scale : 1.0);
             if (max_component(rr) < rr_threshold && s.bounces > 3) {
                 double q = gomath::max(0.05, 1 - max_component(rr));
                 double u1 = c_get1d(c, ss);

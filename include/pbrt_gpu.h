@@ -460,9 +460,17 @@ int pbrt_gpu_query_status(pbrt_gpu_ctx* ctx, pbrt_query_record* out);
  * visibility rays in the high 16. Li does not replace a NaN radiance: that is
  * the Render loop's (integrator.go:256-262), and so the caller's.
  *
- * A ray on which the reference panics has r = g = b = 0, its optional outputs
- * hold the values at the panic, and it is counted in the context's query record
- * (pbrt_gpu_query_status) like a panicking ray of pbrt_gpu_intersect_device.
+ * A ray on which the reference panics has r = g = b = 0 and is counted in the
+ * context's query record (pbrt_gpu_query_status) like a panicking ray of
+ * pbrt_gpu_intersect_device. Its rays output holds the counts at the panic.
+ * state and draws hold the stream at the panic where the closest-hit query of
+ * an iteration panics (it precedes the iteration's draws). Where the light
+ * sample panics (its visibility ray, or UniformSampleOneLight's Ld > 10), the
+ * kernel has already drawn what the reference would have drawn next had it
+ * gone on: the two values of the iteration's BSDF sample and, where Russian
+ * roulette applies (from the fourth iteration on), its one value; the kernels
+ * trace an iteration's visibility ray last. state is rng->state[i] advanced by
+ * draws steps in either case.
  *
  * Ordering and memory are pbrt_gpu_intersect_device's: every pointer is a device
  * pointer to n elements; the call only enqueues on the context's stream, after
@@ -586,9 +594,14 @@ int pbrt_gpu_direct_li_device(pbrt_gpu_ctx* ctx, const pbrt_direct_li_desc* desc
  * length of every array, the queues' index arrays included. An index outside
  * 0 .. n-1 is skipped. After its iteration a path is ALIVE with its next ray in
  * the state, ENDED, or PANICKED: the reference panics in this iteration, lr/lg/lb
- * are set to 0 (as pbrt_gpu_li_device reports such a ray) and the path is counted
+ * are set to 0 (as pbrt_gpu_li_device reports such a ray, state and draws
+ * included) and the path is counted
  * in the context's query record (pbrt_gpu_query_status) under its index, with
- * its PBRT_PANIC_*. With out != NULL the call first zeroes *out->count on the
+ * its PBRT_PANIC_*. A path that is ENDED or PANICKED keeps the ray, beta and
+ * eta_scale its last iteration started from. Every value of the state is the
+ * caller's to set between two steps: a step reads eta_scale on every scene
+ * (Russian roulette compares beta * eta_scale, path.go:145-146), also where no
+ * material of the scene would ever change it. With out != NULL the call first zeroes *out->count on the
  * stream, then the kernel appends the index of every covered path that is ALIVE
  * after the step; the order within out is unspecified, the set is determined.
  * in and out must not share an index or a count array, and the indices of an

@@ -3,6 +3,14 @@
  *
  * C exports used from tests/ (ctypes), __graft_entry__.smoke() and bench.py's
  * cpu_baseline leg. Nothing in go-pbrt_amd/ links or loads this library.
+ *
+ * Besides the render (oracle_render) and the intersection tests on caller rays
+ * (oracle_intersect), the integrators run on caller rays too: oracle_path_li is
+ * Path.Li per ray, from a fresh or a caller's loop state, to the end or for a
+ * limited number of iterations, and oracle_direct_li is DirectLighting.Li per
+ * ray. Both run the functions the render runs (path_li_iteration, direct_li)
+ * with sampler.RandomSampler on each ray's own PCG32 stream, and catch a
+ * reference panic per ray.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -148,6 +156,17 @@ int oracle_intersect(const pbrt_scene_desc* sc, const double* rays, size_t n, in
 }
 void oracle_light_distribution(const pbrt_scene_desc* sc, const pbrt_render_desc* rd, pbrt_distribution_desc* d) {
     orc_light_distribution(sc, rd, d);
+}
+/* the integrators on caller rays (oracle_render.h): the layouts are orc_path_li's and orc_direct_li's */
+int oracle_path_li(const pbrt_scene_desc* sc, int max_depth, int light_strategy, double rr_threshold, size_t n,
+                   const double* rays, const uint64_t* state, const uint64_t* inc, const double* start_f,
+                   const int32_t* start_i, int k, double* out_f, uint64_t* out_state, int32_t* out_i) {
+    return orc_path_li(sc, max_depth, light_strategy, rr_threshold, n, rays, state, inc, start_f, start_i, k, out_f,
+                       out_state, out_i);
+}
+int oracle_direct_li(const pbrt_scene_desc* sc, int max_depth, int dl_strategy, size_t n, const double* rays,
+                     const uint64_t* state, const uint64_t* inc, double* out_L, uint64_t* out_state, int32_t* out_i) {
+    return orc_direct_li(sc, max_depth, dl_strategy, n, rays, state, inc, out_L, out_state, out_i);
 }
 
 /* interaction.go:91-102 SpawnRayToInteraction: in p0 perr0 n0 p1 perr1 n1; out o d tmax */

@@ -1201,14 +1201,27 @@ static spec uniform_sample_one_light(orc_ctx* oc, sampler_t* smp, const si_t* si
 }
 
 /* ============================================================== integrators */
-/* pkg/integrator/path.go:32-157 */
-static spec path_li(orc_ctx* oc, sampler_t* smp, ray_t ray) {
+/* pkg/integrator/path.go:32-157. The loop-carried variables of Path.Li and one
+ * iteration of its loop (path.go:43-155): returns 1 where the reference leaves
+ * the loop, 0 where it goes round again. path_li below is the loop itself;
+ * orc_path_li runs the same body from a caller's state, a limited number of
+ * times. */
+typedef struct {
+    spec L, beta;
+    double eta_scale;
+    int32_t bounces;
+    ray_t ray;
+} path_state_t;
+
+static int path_li_iteration(orc_ctx* oc, sampler_t* smp, path_state_t* st) {
     const pbrt_scene_desc* sc = oc->scene;
     const pbrt_render_desc* rd = oc->rd;
-    spec L = S3(0, 0, 0), beta = S3(1, 1, 1);
-    int32_t bounces = 0;
-    double eta_scale = 1.0;
-    for (;;) {
+    spec L = st->L, beta = st->beta;
+    int32_t bounces = st->bounces;
+    double eta_scale = st->eta_scale;
+    ray_t ray = st->ray;
+    int ended = 1;
+    do {
         bounces++;
         oc->cur_bounce = bounces;
         if (bounces >= rd->max_depth) {          /* path.go:66 (hit or miss)  */
@@ -1266,8 +1279,23 @@ static spec path_li(orc_ctx* oc, sampler_t* smp, ray_t ray) {
             beta = s_divs(beta, 1 - q);
             FL(1);
         }
-    }
-    return L;
+        ended = 0;
+    } while (0);
+    st->L = L; st->beta = beta;
+    st->bounces = bounces;
+    st->eta_scale = eta_scale;
+    st->ray = ray;
+    return ended;
+}
+
+static spec path_li(orc_ctx* oc, sampler_t* smp, ray_t ray) {
+    path_state_t st;
+    st.L = S3(0, 0, 0); st.beta = S3(1, 1, 1);
+    st.bounces = 0;
+    st.eta_scale = 1.0;
+    st.ray = ray;
+    while (!path_li_iteration(oc, smp, &st)) {}
+    return st.L;
 }
 
 /* pkg/integrator/directlighting.go:62-104 DirectLighting.Li at `depth`
@@ -1715,4 +1743,147 @@ int orc_intersect(const pbrt_scene_desc* sc, const double* rays, size_t n, int c
     for (size_t i = 0; i < n; i++)
         intersect_one(&oc, rays + 7 * i, closest, closest ? out + 9 * i : out + i);
     return 0;
+}
+
+/* ------------------------------------------------- per-ray integrator entries
+ * Path.Li and DirectLighting.Li on rays the caller owns, one ray at a time with
+ * sampler.RandomSampler on the ray's own PCG32 stream (every Get1D / Get2D is a
+ * draw). A reference panic is caught per ray, as intersect_one does. */
+typedef struct {
+    sampler_t smp;
+    path_state_t st, at_start;   /* at_start: the state the current iteration began from */
+    spec L;                      /* orc_direct_li */
+    int32_t status;
+} li_work_t;
+
+static void li_ctx(orc_ctx* oc, pbrt_render_desc* rd, const pbrt_scene_desc* sc) {
+    memset(oc, 0, sizeof(*oc));
+    oc->scene = sc;
+    oc->rd = rd;
+    oc->flags = ORACLE_FLAG_RANDOM_SAMPLER;
+    oc->mesh = orc_mesh_get(sc);
+}
+static void li_sampler(sampler_t* smp, uint64_t state, uint64_t inc) {
+    memset(smp, 0, sizeof(*smp));
+    smp->xs = smp->ys = smp->spp = 1;
+    smp->random = 1;
+    smp->rng.state = state;
+    smp->rng.inc = inc;
+}
+static ray_t li_ray(const double* q) {
+    ray_t r;
+    r.o = V3(q[0], q[1], q[2]); r.d = V3(q[3], q[4], q[5]); r.tmax = q[6]; r.time = 0;
+    return r;
+}
+
+/* w lives in the caller's frame, so what a longjmp leaves in it is defined. The
+ * loop counter is this function's own local and changes after setjmp; it is
+ * not read once a longjmp has come back */
+static void path_li_one(orc_ctx* oc, li_work_t* w, int k) {
+    w->status = ORC_PATH_PANICKED;
+    oc->pc.kind = 0;
+    if (setjmp(oc->pc.jb)) return;
+    for (int it = 0; k <= 0 || it < k; it++) {
+        w->at_start = w->st;
+        if (path_li_iteration(oc, &w->smp, &w->st)) { w->status = ORC_PATH_ENDED; return; }
+    }
+    w->status = ORC_PATH_ALIVE;
+}
+
+int orc_path_li(const pbrt_scene_desc* sc, int max_depth, int light_strategy, double rr_threshold, size_t n,
+                const double* rays, const uint64_t* state, const uint64_t* inc, const double* start_f,
+                const int32_t* start_i, int k, double* out_f, uint64_t* out_state, int32_t* out_i) {
+    if (!sc || !rays || !state || !inc || !out_f || !out_state || !out_i || max_depth < 1) return PBRT_E_INVALID;
+    pbrt_render_desc rd;
+    memset(&rd, 0, sizeof(rd));
+    rd.integrator = PBRT_INTEGRATOR_PATH;
+    rd.max_depth = max_depth;
+    rd.light_strategy = light_strategy;
+    rd.rr_threshold = rr_threshold;
+    orc_ctx oc;
+    li_ctx(&oc, &rd, sc);
+    orc_light_distribution(sc, &rd, &oc.dist);
+    li_work_t w;
+    for (size_t i = 0; i < n; i++) {
+        li_sampler(&w.smp, state[i], inc[i]);
+        w.st.L = S3(0, 0, 0); w.st.beta = S3(1, 1, 1);
+        w.st.eta_scale = 1.0;
+        w.st.bounces = 0;
+        uint64_t draws = 0, closest = 0, shadow = 0;
+        if (start_f) {
+            const double* f = start_f + 7 * i;
+            w.st.L = S3(f[0], f[1], f[2]); w.st.beta = S3(f[3], f[4], f[5]);
+            w.st.eta_scale = f[6];
+        }
+        if (start_i) {
+            const int32_t* s = start_i + 4 * i;
+            w.st.bounces = s[0];
+            draws = (uint32_t)s[1]; closest = (uint32_t)s[2]; shadow = (uint32_t)s[3];
+        }
+        w.st.ray = li_ray(rays + 7 * i);
+        w.at_start = w.st;
+        const uint64_t d0 = orc_draws;
+        oc.closest_rays = oc.shadow_rays = 0;
+        path_li_one(&oc, &w, k);
+        if (oc.unsupported) return PBRT_E_UNSUPPORTED;
+        /* a path that is not ALIVE has no next ray: its ray, beta and etaScale read
+         * as its last iteration found them; a panicking path has no L */
+        const path_state_t* r = w.status == ORC_PATH_ALIVE ? &w.st : &w.at_start;
+        const spec L = w.status == ORC_PATH_PANICKED ? S3(0, 0, 0) : w.st.L;
+        double* f = out_f + 14 * i;
+        f[0] = L.c[0]; f[1] = L.c[1]; f[2] = L.c[2];
+        f[3] = r->beta.c[0]; f[4] = r->beta.c[1]; f[5] = r->beta.c[2];
+        f[6] = r->eta_scale;
+        f[7] = r->ray.o.x; f[8] = r->ray.o.y; f[9] = r->ray.o.z;
+        f[10] = r->ray.d.x; f[11] = r->ray.d.y; f[12] = r->ray.d.z;
+        f[13] = r->ray.tmax;
+        out_state[i] = w.smp.rng.state;
+        int32_t* o = out_i + 6 * i;
+        o[0] = w.status == ORC_PATH_PANICKED ? w.at_start.bounces + 1 : w.st.bounces;   /* iterations begun */
+        o[1] = (int32_t)(uint32_t)(draws + (orc_draws - d0));
+        o[2] = (int32_t)(uint32_t)(closest + oc.closest_rays);
+        o[3] = (int32_t)(uint32_t)(shadow + oc.shadow_rays);
+        o[4] = w.status;
+        o[5] = w.status == ORC_PATH_PANICKED ? oc.pc.kind : 0;
+    }
+    return PBRT_OK;
+}
+
+static void direct_li_one(orc_ctx* oc, li_work_t* w) {
+    w->status = ORC_PATH_PANICKED;
+    oc->pc.kind = 0;
+    if (setjmp(oc->pc.jb)) return;
+    w->L = direct_li(oc, &w->smp, w->st.ray);
+    w->status = ORC_PATH_ENDED;
+}
+
+int orc_direct_li(const pbrt_scene_desc* sc, int max_depth, int dl_strategy, size_t n, const double* rays,
+                  const uint64_t* state, const uint64_t* inc, double* out_L, uint64_t* out_state, int32_t* out_i) {
+    if (!sc || !rays || !state || !inc || !out_L || !out_state || !out_i || max_depth < 1) return PBRT_E_INVALID;
+    pbrt_render_desc rd;
+    memset(&rd, 0, sizeof(rd));
+    rd.integrator = PBRT_INTEGRATOR_DIRECT_LIGHTING;
+    rd.max_depth = max_depth;
+    rd.dl_strategy = dl_strategy;
+    orc_ctx oc;
+    li_ctx(&oc, &rd, sc);
+    li_work_t w;
+    for (size_t i = 0; i < n; i++) {
+        li_sampler(&w.smp, state[i], inc[i]);
+        w.st.ray = li_ray(rays + 7 * i);
+        w.L = S3(0, 0, 0);
+        const uint64_t d0 = orc_draws;
+        oc.closest_rays = oc.shadow_rays = 0;
+        direct_li_one(&oc, &w);
+        if (oc.unsupported) return PBRT_E_UNSUPPORTED;
+        const int pan = w.status == ORC_PATH_PANICKED;
+        for (int c = 0; c < 3; c++) out_L[3 * i + c] = pan ? 0.0 : w.L.c[c];
+        out_state[i] = w.smp.rng.state;
+        int32_t* o = out_i + 4 * i;
+        o[0] = (int32_t)(uint32_t)(orc_draws - d0);
+        o[1] = (int32_t)(uint32_t)oc.closest_rays;
+        o[2] = (int32_t)(uint32_t)oc.shadow_rays;
+        o[3] = pan ? oc.pc.kind : 0;
+    }
+    return PBRT_OK;
 }

@@ -50,4 +50,26 @@ int orc_render(const pbrt_scene_desc* sc, const pbrt_render_desc* rd, int n_thre
 int orc_tile_draws(const pbrt_scene_desc* sc, const pbrt_render_desc* rd, int64_t tile, int64_t* out);
 int orc_intersect(const pbrt_scene_desc* sc, const double* rays, size_t n, int closest, double* out);
 
+/* Path.Li (path.go:32-157) on caller rays, ray i with sampler.RandomSampler on the
+ * PCG32 stream (state[i], inc[i]). rays: n x 7 (o, d, TMax).
+ * start_f (n x 7: L, beta, etaScale) and start_i (n x 4: bounces, draws,
+ * closest-hit queries, visibility rays) give the state a path starts from;
+ * NULL is the state Li itself starts from. At most k iterations of the loop
+ * run (k <= 0: to the end), the statements render_tile's path_li runs.
+ * out_f: n x 14 (L, beta, etaScale, the next ray o d TMax); out_state: the
+ * stream's state; out_i: n x 6 (bounces, draws, closest-hit queries,
+ * visibility rays, status ORC_PATH_*, PBRT_PANIC_* kind). A path that is not
+ * ALIVE has no next ray: its ray, beta and etaScale are those its last
+ * iteration started from. A panicking path has L = 0 and its counters and
+ * stream as they stand at the panic. */
+enum { ORC_PATH_ALIVE = 1, ORC_PATH_ENDED = 2, ORC_PATH_PANICKED = 3 };   /* PBRT_PATH_*'s values */
+int orc_path_li(const pbrt_scene_desc* sc, int max_depth, int light_strategy, double rr_threshold, size_t n,
+                const double* rays, const uint64_t* state, const uint64_t* inc, const double* start_f,
+                const int32_t* start_i, int k, double* out_f, uint64_t* out_state, int32_t* out_i);
+/* DirectLighting.Li (directlighting.go:62-104) at depth 0 on the same inputs.
+ * out_L: n x 3; out_i: n x 4 (draws, closest-hit queries, visibility rays,
+ * PBRT_PANIC_* kind); a panicking ray as above. */
+int orc_direct_li(const pbrt_scene_desc* sc, int max_depth, int dl_strategy, size_t n, const double* rays,
+                  const uint64_t* state, const uint64_t* inc, double* out_L, uint64_t* out_state, int32_t* out_i);
+
 #endif

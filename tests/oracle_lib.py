@@ -7,6 +7,7 @@ import ctypes as C
 import os
 import subprocess
 import sys
+from collections import namedtuple
 
 import numpy as np
 
@@ -115,6 +116,10 @@ def _bind(L):
         L.oracle_tile_draws.argtypes = [P(abi.SceneDesc), P(abi.RenderDesc), C.c_int64, P(C.c_int64)]
         L.oracle_light_distribution.argtypes = [P(abi.SceneDesc), P(abi.RenderDesc), P(abi.DistributionDesc)]
         L.oracle_spawn_ray_to.argtypes = [P(d), P(d)]
+        u64p, i32p = P(C.c_uint64), P(C.c_int32)
+        L.oracle_path_li.argtypes = [P(abi.SceneDesc), C.c_int, C.c_int, d, C.c_size_t, P(d), u64p, u64p, P(d), i32p,
+                                     C.c_int, P(d), u64p, i32p]
+        L.oracle_direct_li.argtypes = [P(abi.SceneDesc), C.c_int, C.c_int, C.c_size_t, P(d), u64p, u64p, P(d), u64p, i32p]
         L.oracle_triangle_hit.argtypes = [P(d), P(d), P(d)]
         L.oracle_triangle_hits.argtypes = [P(d), C.c_int64, P(d), P(C.c_uint8), P(d)]
         L.oracle_triangle_hits.restype = C.c_int64
@@ -198,6 +203,71 @@ def intersect(desc, rays, closest=True):
     n = rays.shape[0]
     out = np.zeros((n, 9) if closest else (n,), dtype=np.float64)
     lib().oracle_intersect(C.byref(desc), dptr(rays), n, 1 if closest else 0, dptr(out))
+    return out
+
+
+ALIVE, ENDED, PANICKED = 1, 2, 3   # PathLi.status (PBRT_PATH_*'s values)
+PathLi = namedtuple("PathLi", "L beta eta_scale ray bounces state draws closest shadow status panic")
+DirectLi = namedtuple("DirectLi", "L state draws closest shadow panic")
+PathStart = namedtuple("PathStart", "L beta eta_scale bounces draws closest shadow")
+
+
+def _streams(rays, state, inc):
+    rays = np.ascontiguousarray(rays, dtype=np.float64)
+    assert rays.ndim == 2 and rays.shape[1] == 7
+    state, inc = np.ascontiguousarray(state, dtype=np.uint64), np.ascontiguousarray(inc, dtype=np.uint64)
+    assert state.shape == inc.shape == (rays.shape[0],)
+    return rays, state, inc
+
+
+def _u64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint64))
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def path_li(desc, rays, state, inc, max_depth=5, light_strategy=0, rr_threshold=1.0, k=0, start=None):
+    """oracle_path_li: Path.Li on the rays (n, 7: o, d, TMax), ray i with RandomSampler on the PCG32
+    stream (state[i], inc[i]), from the fresh state or from `start` (a PathStart, or a PathLi of an
+    earlier call: its L, beta, eta_scale, bounces and counters), for at most k iterations (k <= 0:
+    to the end). Returns a PathLi of arrays: L, beta (n, 3); ray (n, 7), the next ray; status
+    ALIVE / ENDED / PANICKED and panic, the PBRT_PANIC_* kind. A path that is not ALIVE keeps the
+    ray, beta and eta_scale its last iteration started from; a PANICKED path has L = 0 and its
+    counters and stream as at the panic."""
+    rays, state, inc = _streams(rays, state, inc)
+    n = rays.shape[0]
+    sf = si = None
+    if start is not None:
+        sf = np.ascontiguousarray(np.concatenate([start.L, start.beta, np.asarray(start.eta_scale)[:, None]], axis=1),
+                                  dtype=np.float64)
+        si = np.ascontiguousarray(np.stack([start.bounces, start.draws, start.closest, start.shadow], axis=1), dtype=np.int32)
+        assert sf.shape == (n, 7) and si.shape == (n, 4)
+    of, ost, oi = np.zeros((n, 14)), np.zeros(n, dtype=np.uint64), np.zeros((n, 6), dtype=np.int32)
+    rc = lib().oracle_path_li(C.byref(desc), max_depth, light_strategy, rr_threshold, n, dptr(rays), _u64p(state), _u64p(inc),
+                              dptr(sf) if sf is not None else None, _i32p(si) if si is not None else None, k,
+                              dptr(of), _u64p(ost), _i32p(oi))
+    assert rc == 0, rc
+    out = PathLi(of[:, 0:3].copy(), of[:, 3:6].copy(), of[:, 6].copy(), of[:, 7:14].copy(), oi[:, 0].copy(), ost,
+                 oi[:, 1].astype(np.uint32), oi[:, 2].astype(np.uint32), oi[:, 3].astype(np.uint32),
+                 oi[:, 4].astype(np.uint8), oi[:, 5].copy())
+    for a in out:
+        a.setflags(write=False)
+    return out
+
+
+def direct_li(desc, rays, state, inc, max_depth=5, dl_strategy=0):
+    """oracle_direct_li: DirectLighting.Li at depth 0 on the same inputs. Returns a DirectLi."""
+    rays, state, inc = _streams(rays, state, inc)
+    n = rays.shape[0]
+    oL, ost, oi = np.zeros((n, 3)), np.zeros(n, dtype=np.uint64), np.zeros((n, 4), dtype=np.int32)
+    rc = lib().oracle_direct_li(C.byref(desc), max_depth, dl_strategy, n, dptr(rays), _u64p(state), _u64p(inc),
+                                dptr(oL), _u64p(ost), _i32p(oi))
+    assert rc == 0, rc
+    out = DirectLi(oL, ost, oi[:, 0].astype(np.uint32), oi[:, 1].astype(np.uint32), oi[:, 2].astype(np.uint32), oi[:, 3].copy())
+    for a in out:
+        a.setflags(write=False)
     return out
 
 
