@@ -15,6 +15,7 @@ using ChainKernel = decltype(&k_chain_ci<1>);
 using PathsCiKernel = decltype(&k_paths_ci<4>);
 using PathsCamKernel = decltype(&k_paths_cam<4, false>);
 using LiKernel = decltype(&k_li<false, 0>);
+using LiStratKernel = decltype(&k_li_strat<false, 0>);
 using DirectLiKernel = decltype(&k_li_direct<false, 0>);
 using PathStepKernel = decltype(&k_path_step<false, 0>);
 using SerialKernel = decltype(&k_render_exact<1>);
@@ -26,6 +27,7 @@ int paths_ci_lds(int P, int staged_values);
 PathsCamKernel paths_cam_kernel(int P, bool mb, bool stack);   // stack: k_paths_cam_stack
 // the device queries: kDepth 0 on an LDS-staged tree, 64 beyond (li_query.h: kernel_args)
 LiKernel li_kernel(bool kx, int depth);
+LiStratKernel li_strat_kernel(bool kx, int depth);
 DirectLiKernel direct_li_kernel(bool kx, int depth);
 PathStepKernel path_step_kernel(bool kx, int depth);
 SerialKernel serial_kernel(int min_waves);   // the amdgpu_waves_per_eu builds of k_render_exact

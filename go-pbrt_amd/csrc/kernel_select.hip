@@ -59,13 +59,14 @@ const PathsCamRow kPathsCamKernels[] = {   // stack: the k_paths_cam_stack kerne
 };
 #undef PATHS_CAM_ROWS
 
-// The device queries' families (k_li, k_li_direct, k_path_step) are each instantiated over
+// The device queries' families (k_li, k_li_strat, k_li_direct, k_path_step) are each instantiated over
 // <kX, kDepth> alike: one row type, one set of rows, one lookup.
 template <class K>
 struct QueryRow { bool kx; int depth; K fn; const char* name; };
 #define QUERY_ROW(k, kx, depth) {kx, depth, &k<kx, depth>, #k "<" #kx ", " #depth ">"}
 #define QUERY_ROWS(k) {QUERY_ROW(k, false, 0), QUERY_ROW(k, true, 0), QUERY_ROW(k, false, 64), QUERY_ROW(k, true, 64)}
 const QueryRow<LiKernel> kLiKernels[] = QUERY_ROWS(k_li);
+const QueryRow<LiStratKernel> kLiStratKernels[] = QUERY_ROWS(k_li_strat);
 const QueryRow<DirectLiKernel> kDirectLiKernels[] = QUERY_ROWS(k_li_direct);
 const QueryRow<PathStepKernel> kPathStepKernels[] = QUERY_ROWS(k_path_step);
 #undef QUERY_ROWS
@@ -106,6 +107,7 @@ PathsCamKernel paths_cam_kernel(int P, bool mb, bool stack) {
 }
 
 LiKernel li_kernel(bool kx, int depth) { return query_kernel(kLiKernels, kx, depth); }
+LiStratKernel li_strat_kernel(bool kx, int depth) { return query_kernel(kLiStratKernels, kx, depth); }
 DirectLiKernel direct_li_kernel(bool kx, int depth) { return query_kernel(kDirectLiKernels, kx, depth); }
 PathStepKernel path_step_kernel(bool kx, int depth) { return query_kernel(kPathStepKernels, kx, depth); }
 
@@ -122,7 +124,7 @@ SerialKernel serial_kernel(int min_waves) {
 // ---- the launch log (pbrt_diag.h): names by host function pointer. One entry per
 // kernel the library compiles, spelled as its explicit instantiation is
 // (tests/test_kernel_manifest.py compares the names with the sources). The k_chain_ci,
-// k_paths_ci, k_paths_cam[_stack], k_li, k_li_direct and k_path_step families are named by their selectors' tables.
+// k_paths_ci, k_paths_cam[_stack], k_li, k_li_strat, k_li_direct and k_path_step families are named by their selectors' tables.
 namespace {
 const KernelName kKernelNames[] = {
     // k_paths_m.hip, k_paths_x.hip
@@ -187,6 +189,8 @@ const KernelName kKernelNames[] = {
     PBRT_KERNEL_NAME(k_film_rgba8),
     // k_path_step.hip
     PBRT_KERNEL_NAME(k_path_begin),
+    // k_strat.hip
+    PBRT_KERNEL_NAME(k_strat_pixels),
 };
 
 template <class F>
@@ -195,6 +199,7 @@ void each_kernel(F f) {   // f(pointer, name) of every kernel: the selectors' ta
     for (const PathsCiRow& r : kPathsCiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const PathsCamRow& r : kPathsCamKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const auto& r : kLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
+    for (const auto& r : kLiStratKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const auto& r : kDirectLiKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const auto& r : kPathStepKernels) f(reinterpret_cast<const void*>(r.fn), r.name);
     for (const KernelName& k : kKernelNames) f(k.fn, k.name);
@@ -239,6 +244,8 @@ extern "C" const char* pbrt_diag_kernel_choice(const char* family, const int* a,
         fn = reinterpret_cast<const void*>(serial_kernel(a[0]));
     else if (f == "k_li" && n == 2)
         fn = reinterpret_cast<const void*>(li_kernel(a[0] != 0, a[1]));
+    else if (f == "k_li_strat" && n == 2)
+        fn = reinterpret_cast<const void*>(li_strat_kernel(a[0] != 0, a[1]));
     else if (f == "k_li_direct" && n == 2)
         fn = reinterpret_cast<const void*>(direct_li_kernel(a[0] != 0, a[1]));
     else if (f == "k_path_step" && n == 2)

@@ -4,7 +4,7 @@
 // pieces, the queries' panic record and the buffers a context owns
 // (include/pbrt_gpu.h). The checks, the kernel choices and the grids that need
 // no device are in the HIP-free headers li_query.h, direct_li_query.h,
-// path_query.h, film_query.h and query_buffers.h.
+// path_query.h, film_query.h, strat_query.h and query_buffers.h.
 #pragma clang fp contract(off)
 
 #include "../../include/pbrt_diag.h"
@@ -13,6 +13,7 @@
 #include "film_query.h"
 #include "kernel_select.h"
 #include "path_query.h"
+#include "strat_query.h"
 
 using namespace pbrt;
 using namespace pbrtk;
@@ -308,6 +309,45 @@ int pbrt_gpu_frame_samples_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, con
     const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
     launch_k(c, k_frame_samples, dim3((unsigned)((n + kQueryBlock - 1) / kQueryBlock)), dim3(kQueryBlock), 0, c->stream,
              c->d_camera.get(), l, pbrtfilm::pixels_before(l, d->tile_begin), (int)d->ns, n, *out);
+    return launched(c);
+}
+
+// ---- the same pieces under sampler.Stratified (k_strat.hip). The checks, the StartPixel plan and the
+// kernel choice: strat_query.h.
+int pbrt_gpu_frame_samples_stratified_device(pbrt_gpu_ctx* c, const pbrt_frame_desc* d, const pbrt_strat_sampler_desc* s,
+                                             const pbrt_frame_samples_soa* out, const pbrt_strat_samples_soa* strat) {
+    const char* why = "";
+    int64_t n = 0;
+    const pbrt_film_desc* f = c ? &c->host_scene.film : nullptr;
+    if (int rc = pbrtstrat::check_samples_args(c != nullptr, f, d, s, out, strat, c && query_blocked(c), &n, &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtstrat::check_samples_supported(c->facts, c->knobs, *f, *d, *s, &why)) return set_err(c, rc, why);
+    if (n == 0) return PBRT_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const pbrtfilm::Layout l = pbrtfilm::layout(*f, d->tile_size);
+    const pbrtstrat::Plan p = pbrtstrat::plan(c->facts, c->knobs, *f, *d, *s);
+    const int64_t npx = n / d->ns;
+    launch_k(c, k_strat_pixels, dim3((unsigned)npx), dim3(kWave), (unsigned)p.lay.total, c->stream, c->d_camera.get(), p.rp,
+             p.lay, c->d_jump.get(), l, pbrtfilm::pixels_before(l, d->tile_begin), npx, *out, *strat);
+    return launched(c);
+}
+
+int pbrt_gpu_li_stratified_device(pbrt_gpu_ctx* c, const pbrt_li_desc* d, const pbrt_ray_soa* rays, const pbrt_rng_soa* rng,
+                                  size_t n, const pbrt_radiance_soa* out, const pbrt_strat_soa* strat) {
+    const char* why = "";
+    if (int rc = pbrtstrat::check_li_args(c != nullptr, d, rays, rng, n, out, strat, c && query_blocked(c), &why))
+        return set_err(c, rc, why);
+    if (int rc = pbrtli::check_supported(*d, c->facts.rough_glass, &why)) return set_err(c, rc, why);
+    if (int rc = li_distribution(c, d, n)) return rc;
+    if (n == 0) return PBRT_OK;
+    DevScene sc;
+    if (int rc = query_begin(c, true, sc)) return rc;
+    const pbrtli::KernelArgs ka =
+        pbrtstrat::kernel_args(c->facts.non_matte, c->host_scene.n_nodes, c->mesh.n_nodes != 0, n, kLdsNodes);
+    const LiStratKernel kern = li_strat_kernel(ka.kx, ka.depth);
+    if (!kern) return set_err(c, PBRT_E_HIP, "no k_li_strat instantiation for depth " + std::to_string(ka.depth));
+    launch_k(c, kern, dim3(ka.grid), dim3(kWave), 0, c->stream, sc, (int)d->max_depth, d->rr_threshold, (int64_t)n,
+             *rays, *rng, *out, *strat, c->d_qrec.get());
     return launched(c);
 }
 

@@ -78,5 +78,9 @@ template <bool kLds>
 __global__ void k_film_add_tiles(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, pbrtfilm::Layout lay, int64_t tile_begin, int ns, pbrt_film_samples_soa in, double* __restrict__ films);
 __global__ void k_film_add_merge(const pbrt_film_desc* __restrict__ film_desc, RenderParams rp, int64_t tile_begin, int64_t tile_end, int64_t row0, int64_t rows, int clear, const double* __restrict__ films, double* __restrict__ out);
 __global__ void k_film_rgba8(const double* __restrict__ film, int64_t n, uint32_t* __restrict__ rgba);
+// the same pieces under sampler.Stratified (pbrt_gpu_frame_samples_stratified_device, pbrt_gpu_li_stratified_device): k_strat.hip
+__global__ void k_strat_pixels(const pbrt_camera_desc* __restrict__ cam, RenderParams rp, ChainLayout lay, const PcgJump* __restrict__ jump, pbrtfilm::Layout fl, int64_t px_begin, int64_t npx, pbrt_frame_samples_soa out, pbrt_strat_samples_soa so);
+template <bool kX, int kDepth>
+__global__ void k_li_strat(DevScene sc, int max_depth, double rr_threshold, int64_t n, pbrt_ray_soa rays, pbrt_rng_soa rng, pbrt_radiance_soa out, pbrt_strat_soa st, QueryRec* __restrict__ rec);
 
 }  // namespace pbrtk

@@ -23,6 +23,7 @@
 #include "k_li_direct.hip"
 #include "k_path_step.hip"
 #include "k_film_q.hip"
+#include "k_strat.hip"
 #include "kernel_select.hip"
 #include "render.hip"
 #include "queries.hip"

@@ -74,6 +74,8 @@ def lib():
         abi.declare_frame(L)
     if hasattr(L, "pbrt_gpu_path_step_device"):
         abi.declare_path(L)
+    if hasattr(L, "pbrt_gpu_li_stratified_device"):
+        abi.declare_strat(L)
     abi.declare_launch_log(L)
     abi.declare_probe(L)
     L.pbrt_film_to_rgba8.argtypes = [P(d), i64, i64, P(C.c_uint8)]
@@ -475,6 +477,8 @@ SAMPLE_DTYPES = {**{k: np.float64 for k in RAY_KEYS + ("tmax", "pfilm_x", "pfilm
 SAMPLE_REQUIRED = RAY_KEYS + ("pfilm_x", "pfilm_y", "state", "inc")
 FILM_KEYS = ("pfilm_x", "pfilm_y", "r", "g", "b")
 FRAME_BYTES_PER_SAMPLE = 8 * (len(SAMPLE_REQUIRED) + 3)   # a composed frame's arrays: 104 B (render_samples)
+STRAT_SAMPLE_KEYS = ("k", "table")   # int32 per sample; "s1d": float64, n_dims * spp per pixel of the range
+STRAT_BYTES_PER_SAMPLE = FRAME_BYTES_PER_SAMPLE + 8   # with k and table: 112 B (render_samples_stratified)
 
 
 class DeviceBuffer:
@@ -1135,6 +1139,137 @@ class Renderer:
         if count_rays:
             info.update(closest_rays=closest, shadow_rays=shadow)
         return out, info
+
+    # ---- the same pieces under sampler.Stratified
+    def frame_samples_stratified(self, out, strat, sampler_x, sampler_y, n_dims, jitter=False, tile_begin=0,
+                                 tile_end=None, tile_size=16):
+        """pbrt_gpu_frame_samples_stratified_device: the traced samples (k = 1 .. spp - 1) of a
+        THROUGHPUT render under Stratified(sampler_x, sampler_y, jitter, n_dims), n_dims >= 1, over a
+        tile range. out: frame_samples' buffers; strat: k and table (int32 per sample) and s1d
+        (float64, n_dims * spp per pixel of the range: the pixels' tables). Enqueue only. Returns
+        the status (PBRT_E_UNSUPPORTED: last_error() says why)."""
+        unknown = (set(out) - set(SAMPLE_DTYPES)) | (set(strat) - set(STRAT_SAMPLE_KEYS) - {"s1d"})
+        missing = [k for k in SAMPLE_REQUIRED if out.get(k) is None] + \
+                  [k for k in STRAT_SAMPLE_KEYS + ("s1d",) if strat.get(k) is None]
+        if unknown or missing:
+            raise PbrtError(abi.PBRT_E_INVALID, f"frame_samples_stratified: unknown {sorted(unknown)}, missing {missing}")
+        spp = int(sampler_x) * int(sampler_y)
+        d, n = self._frame_desc("frame_samples_stratified", spp - 1, tile_begin, tile_end, tile_size)
+        npx = n // (spp - 1) if spp > 1 else 0
+        ob = [(k, out[k], dt) for k, dt in SAMPLE_DTYPES.items() if out.get(k) is not None]
+        kb = [(k, strat[k], np.int32) for k in STRAT_SAMPLE_KEYS]
+        check_buffers(self, n, ob + kb)
+        check_buffers(self, npx * max(int(n_dims), 0) * spp, [("s1d", strat["s1d"], np.float64)])
+        s = abi.strat_sampler_desc(sampler_x, sampler_y, n_dims, jitter)
+        os_, ss = _soa(abi.FrameSamplesSoA, ob), _soa(abi.StratSamplesSoA, kb + [("s1d", strat["s1d"], np.float64)])
+        return lib().pbrt_gpu_frame_samples_stratified_device(self.h, C.byref(d), C.byref(s), C.byref(os_), C.byref(ss))
+
+    def li_stratified_device(self, rays, rng, n, out, strat, n_tables, spp, n_dims, first_1d, first_2d, max_depth=10,
+                             light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0,
+                             integrator=abi.PBRT_INTEGRATOR_PATH):
+        """pbrt_gpu_li_stratified_device: li_device under the stratified sampler. strat: s1d (float64,
+        n_tables tables of n_dims * spp), table and k (int32 per ray); first_1d, first_2d: the
+        dimensions the rays' first Get1D / Get2D read. With n_dims = 0 strat may be empty. The other
+        arguments, the outputs and the buffer checks are li_device's. Returns the status."""
+        rs, gs, os_ = _li_soas(self, "li_stratified_device", rays, rng, n, out)
+        unknown = set(strat) - set(STRAT_SAMPLE_KEYS) - {"s1d"}
+        if unknown:
+            raise PbrtError(abi.PBRT_E_INVALID, f"li_stratified_device: unknown {sorted(unknown)}")
+        kb = [(k, strat[k], np.int32) for k in STRAT_SAMPLE_KEYS if strat.get(k) is not None]
+        check_buffers(self, n, kb)
+        tb = [("s1d", strat["s1d"], np.float64)] if strat.get("s1d") is not None else []
+        if min(int(n_tables), int(spp), int(n_dims)) > 0:
+            check_buffers(self, int(n_tables) * int(n_dims) * int(spp), tb)
+        ss = _soa(abi.StratSoA, kb + tb)
+        ss.n_tables, ss.spp, ss.n_dims, ss.first_1d, ss.first_2d = n_tables, spp, n_dims, first_1d, first_2d
+        d = abi.li_desc(max_depth, light_strategy, rr_threshold, integrator)
+        return lib().pbrt_gpu_li_stratified_device(self.h, C.byref(d), C.byref(rs), C.byref(gs), n, C.byref(os_),
+                                                   C.byref(ss))
+
+    def frame_ranges_stratified(self, spp, n_dims, tile_size=16, budget_bytes=1 << 30):
+        """frame_ranges for a stratified frame: a pixel takes its spp - 1 samples of
+        STRAT_BYTES_PER_SAMPLE bytes and its table of n_dims * spp doubles."""
+        nt, ns = self.num_tiles(tile_size), spp - 1
+        per_px = STRAT_BYTES_PER_SAMPLE * ns + 8 * n_dims * spp
+        per = max(1, int(budget_bytes) // (per_px * tile_size * tile_size))
+        return [(b, min(b + per, nt), self.frame_count(ns, b, min(b + per, nt), tile_size)) for b in range(0, nt, per)]
+
+    def render_samples_stratified(self, sampler_x, sampler_y, n_dims, jitter=False, max_depth=10,
+                                  light_strategy=abi.PBRT_LIGHT_STRATEGY_UNIFORM, rr_threshold=1.0, tile_size=16,
+                                  budget_bytes=1 << 30, film=None, count_rays=False):
+        """A THROUGHPUT Path frame under Stratified(sampler_x, sampler_y, jitter, n_dims), n_dims >= 1,
+        composed of the public stages: per ascending tile range sized to budget_bytes,
+        frame_samples_stratified, li_stratified_device with the cursors after the camera sample, and
+        film_add, all on the device; the film is pbrt_gpu_render's, bit for bit. Arguments and the
+        returned (film, info) are render_samples'."""
+        spp = int(sampler_x) * int(sampler_y)
+        ns = spp - 1
+        if ns < 1 or n_dims < 1:
+            raise PbrtError(abi.PBRT_E_INVALID, "render_samples_stratified: spp >= 2 (sample 0 of a pixel is never "
+                                                "traced) and n_dims >= 1 (n_dims = 0 is render_samples)")
+        ranges = self.frame_ranges_stratified(spp, n_dims, tile_size, budget_bytes)
+        cap = max(n for _, _, n in ranges)
+        c1, c2 = abi.camera_cursors(n_dims)
+        own = []
+        try:
+            if film is None:
+                film = self.buffer(self.hgt * self.w * 3)
+                own.append(film)
+            sb = {k: self.buffer(cap, SAMPLE_DTYPES[k]) for k in SAMPLE_REQUIRED}
+            ob = {k: self.buffer(cap) for k in ("r", "g", "b")}
+            if count_rays:
+                ob["rays"] = self.buffer(cap, np.uint32)
+            kb = {k: self.buffer(cap, np.int32) for k in STRAT_SAMPLE_KEYS}
+            kb["s1d"] = self.buffer((cap // ns) * n_dims * spp)
+            own += list(sb.values()) + list(ob.values()) + list(kb.values())
+            rays = {k: sb[k] for k in RAY_KEYS}
+            rng = {k: sb[k] for k in RNG_KEYS}
+            fs = dict(pfilm_x=sb["pfilm_x"], pfilm_y=sb["pfilm_y"], r=ob["r"], g=ob["g"], b=ob["b"])
+            closest = shadow = 0
+            for i, (b, e, n) in enumerate(ranges):
+                self._check(self.frame_samples_stratified(sb, kb, sampler_x, sampler_y, n_dims, jitter, b, e, tile_size))
+                self._check(self.li_stratified_device(rays, rng, n, ob, kb, n // ns, spp, n_dims, c1, c2, max_depth,
+                                                      light_strategy, rr_threshold))
+                self._check(self.film_add(fs, ns, film, b, e, tile_size, clear=i == 0))
+                if count_rays:
+                    v = ob["rays"].download()[:n]
+                    closest += int((v & 0xFFFF).sum())
+                    shadow += int((v >> 16).sum())
+            rc, rec = self.query_status()
+            if rc:
+                raise PbrtError(rc, self.last_error(), rec)
+            out = film.download()[:self.hgt * self.w * 3].reshape(self.hgt, self.w, 3)
+        finally:
+            for b in own:
+                b.close()
+        info = {"ranges": len(ranges), "samples": sum(n for _, _, n in ranges)}
+        if count_rays:
+            info.update(closest_rays=closest, shadow_rays=shadow)
+        return out, info
+
+    def radiance_stratified(self, rays, state, inc, s1d, table, k, first_1d, first_2d, **desc):
+        """Path.Li of host rays under the stratified sampler, in the shape of radiance: s1d is
+        (n_tables, n_dims, spp) float64, table and k the table and sample index of each ray (int32),
+        first_1d / first_2d the starting cursors; desc is li_device's. Returns (L (n, 3), state,
+        draws, rays)."""
+        s1d = np.ascontiguousarray(s1d, dtype=np.float64)
+        if s1d.ndim != 3 or len(table) != len(state) or len(k) != len(state):
+            raise PbrtError(abi.PBRT_E_INVALID, "radiance_stratified: s1d (n_tables, n_dims, spp), table and k of n elements")
+        n_tables, n_dims, spp = s1d.shape
+        bufs = []
+
+        def query(rb, gb, n, ob, **dd):
+            st = {}
+            if s1d.size:
+                st = dict(s1d=self.upload(s1d.reshape(-1)), table=self.upload(np.asarray(table, dtype=np.int32)),
+                          k=self.upload(np.asarray(k, dtype=np.int32)))
+                bufs.extend(st.values())
+            return self.li_stratified_device(rb, gb, n, ob, st, n_tables, spp, n_dims, first_1d, first_2d, **dd)
+        try:
+            return self._host_radiance("radiance_stratified", query, rays, state, inc, desc)
+        finally:
+            for b in bufs:
+                b.close()
 
     def radiance(self, rays, state, inc, **desc):
         """Path.Li of host rays: rays is (n, 6) [ox, oy, oz, dx, dy, dz] or (n, 7) with tmax,

@@ -523,6 +523,46 @@ def declare_frame(L):
     L.pbrt_gpu_film_scratch_bytes.restype = C.c_size_t
 
 
+# ------------------- the same pieces under sampler.Stratified (include/pbrt_gpu.h)
+class StratSamplerDesc(C.Structure):
+    """pbrt_strat_sampler_desc: sampler.NewStratified(sampler_x, sampler_y, jitter, n_dims)."""
+    _fields_ = [("sampler_x", C.c_int32), ("sampler_y", C.c_int32), ("n_dims", C.c_int32), ("jitter", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class StratSamplesSoA(C.Structure):
+    """pbrt_strat_samples_soa: k and table per sample, s1d per pixel of the range (all required)."""
+    _fields_ = [("k", C.POINTER(C.c_int32)), ("table", C.POINTER(C.c_int32)), ("s1d", C.POINTER(C.c_double))]
+
+
+class StratSoA(C.Structure):
+    """pbrt_strat_soa: the tables, the per-ray table and sample indices and the per-call cursors."""
+    _fields_ = [("s1d", C.POINTER(C.c_double)), ("table", C.POINTER(C.c_int32)), ("k", C.POINTER(C.c_int32)),
+                ("n_tables", C.c_int32), ("spp", C.c_int32), ("n_dims", C.c_int32), ("first_1d", C.c_int32),
+                ("first_2d", C.c_int32), ("reserved", C.c_int32)]
+
+
+STRAT_SYMBOLS = ("pbrt_gpu_frame_samples_stratified_device", "pbrt_gpu_li_stratified_device")
+
+
+def strat_sampler_desc(sampler_x, sampler_y, n_dims, jitter=False, reserved=0):
+    return StratSamplerDesc(sampler_x, sampler_y, n_dims, 1 if jitter else 0, reserved)
+
+
+def camera_cursors(n_dims):
+    """(first_1d, first_2d) of a path after GetCameraSample: pFilm, pLens (Get2D) and the time (Get1D)."""
+    return min(1, n_dims), min(2, n_dims)
+
+
+def declare_strat(L):
+    """ctypes prototypes of the stratified calls (apart, like declare_li: an earlier build has none)."""
+    P, vp = C.POINTER, C.c_void_p
+    L.pbrt_gpu_frame_samples_stratified_device.argtypes = [vp, P(FrameDesc), P(StratSamplerDesc), P(FrameSamplesSoA),
+                                                           P(StratSamplesSoA)]
+    L.pbrt_gpu_li_stratified_device.argtypes = [vp, P(LiDesc), P(RaySoA), P(RngSoA), C.c_size_t, P(RadianceSoA),
+                                                P(StratSoA)]
+
+
 # pbrt_gpu_probe ops (include/pbrt_diag.h): one device function on a batch of inputs
 PBRT_PROBE_SIN = 1
 PBRT_PROBE_COS = 2

@@ -717,8 +717,9 @@ int64_t pbrt_gpu_frame_count(const pbrt_gpu_ctx* ctx, const pbrt_frame_desc* des
  * pfilm_x, pfilm_y, the absolute raster position (double)px + the drawn offset;
  * state, the stream after the five draws, where pbrt_gpu_li_device begins; inc;
  * and, where not NULL, the pixel px, py. One kernel launch (k_frame_samples).
- * Not served: the samples of n_dims >= 1, whose camera values are stratified,
- * and EXACT mode, where a tile's samples share one stream. */
+ * The samples of n_dims >= 1, whose camera values are stratified, are
+ * pbrt_gpu_frame_samples_stratified_device's. Not served: EXACT mode, where a
+ * tile's samples share one stream. */
 typedef struct pbrt_frame_samples_soa {
     double *ox, *oy, *oz, *dx, *dy, *dz;
     double *tmax;                /* may be NULL                              */
@@ -766,6 +767,91 @@ int pbrt_gpu_film_add_device(pbrt_gpu_ctx* ctx, const pbrt_frame_desc* desc,
  * h <= 0, more than 2^31 - 1 pixels, a render in flight. */
 int pbrt_gpu_film_rgba8_device(pbrt_gpu_ctx* ctx, const double* film_device, int64_t w, int64_t h,
                                uint8_t* rgba_device);
+
+/* ------------------------------------ the same pieces under sampler.Stratified
+ * pbrt_gpu_frame_samples_device and pbrt_gpu_li_device speak sampler.RandomSampler:
+ * every Get1D / Get2D is a PCG32 draw. The two calls below are their forms under
+ * sampler.NewStratified(sampler_x, sampler_y, jitter, n_dims) (pixel.go:60-80,
+ * stratified.go:21-48): a pixel has n_dims shuffled 1D arrays of spp = sampler_x
+ * * sampler_y values, made by StartPixel; Get1D returns samples1D[cur1d++][k]
+ * while cur1d < n_dims and is a draw beyond; Get2D returns samples2D[cur2d++][k]
+ * while cur2d < n_dims and is two draws beyond, and every stratified 2D value is
+ * (0, 0) (StratifiedSample2D writes into a copy, sampling.go:122-124). A path is
+ * therefore described by its ray, its PCG32 stream, its pixel's table of n_dims x
+ * spp doubles, its sample index k and the two dimension cursors it starts from.
+ * With pbrt_gpu_film_add_device the composed film is a THROUGHPUT render's with
+ * the same sampler, bit for bit. Ordering and memory are the frame calls'.
+ *
+ * pbrt_gpu_frame_samples_stratified_device: the traced samples of a THROUGHPUT
+ * render with n_dims >= 1 in the frame layout, ns = spp - 1, position j of a
+ * pixel holding its sample k = j + 1. StartPixel of pixel pi of tile t runs on
+ * the stream mb_state(t, pi, 0), sample k on mb_state(t, pi, k), both with inc =
+ * 2 t + 1. The camera sample is GetCameraSample's (sampler.go:75-80): pFilm is
+ * the stratified (0, 0); pLens is (0, 0) for n_dims >= 2 and two draws for
+ * n_dims = 1 (drawn with or without a lens, used only with one); the time is
+ * s1d[0][k], which reaches no draw and no output. Written per sample, in out: the
+ * ray, pfilm_x / pfilm_y = (double)px, (double)py, state (the stream after the
+ * camera sample's draws, where Li begins), inc, and px / py where not NULL; in
+ * strat: k, the sample index, and table, the index of the sample's pixel within
+ * the range (its position in the frame layout with one element a pixel). Written
+ * per pixel of the range, in layout order: its table s1d[pixel][d * spp + k], the
+ * values StartPixel leaves, all spp columns (pbrt_gpu_frame_count with ns = 1
+ * gives the pixel count). After the camera sample the cursors of a path are
+ * (min(1, n_dims), min(2, n_dims)): what pbrt_gpu_li_stratified_device takes as
+ * first_1d, first_2d. One kernel launch (k_strat_pixels), one wave per pixel.
+ *
+ * PBRT_E_INVALID: the frame calls' own cases; a NULL sampler; sampler_x or
+ * sampler_y < 1; the sampler's reserved != 0; ns != sampler_x * sampler_y - 1; a
+ * NULL out, strat or required pointer (all of strat's are required).
+ * PBRT_E_UNSUPPORTED, with the reason in pbrt_gpu_last_error: the frame calls'
+ * own; n_dims < 1 (that frame is pbrt_gpu_frame_samples_device's); and the wave
+ * StartPixel's limits, as for a render: spp > 4096, n_dims * spp > 8192, or a
+ * StartPixel staging beyond 48 KB of LDS. */
+typedef struct pbrt_strat_sampler_desc {
+    int32_t sampler_x, sampler_y;   /* >= 1; spp = sampler_x * sampler_y          */
+    int32_t n_dims;                 /* >= 1                                       */
+    int32_t jitter;                 /* 0 / 1                                      */
+    int32_t reserved;               /* 0                                          */
+} pbrt_strat_sampler_desc;
+typedef struct pbrt_strat_samples_soa {
+    int32_t *k, *table;          /* per sample                                    */
+    double *s1d;                 /* per pixel of the range: n_dims * spp          */
+} pbrt_strat_samples_soa;
+int pbrt_gpu_frame_samples_stratified_device(pbrt_gpu_ctx* ctx, const pbrt_frame_desc* desc,
+                                             const pbrt_strat_sampler_desc* sampler,
+                                             const pbrt_frame_samples_soa* out,
+                                             const pbrt_strat_samples_soa* strat);
+
+/* pbrt_gpu_li_device under the stratified sampler: ray i gets Path.Li(ray_i,
+ * scene, sampler, 0), where the sampler is a PixelSampler with the tables
+ * s1d[table[i]] (n_dims * spp doubles each, value [d * spp + k]), at sample
+ * k[i], with its cursors at (first_1d, first_2d) -- the dimensions the ray's
+ * first Get1D / Get2D read -- on the stream (rng->state[i], rng->inc[i]).
+ * out->draws counts PCG32 draws only (a stratified value consumes none);
+ * out->state is the input state advanced by draws. The panic record, the
+ * optional outputs, the light distributions and the refusals are
+ * pbrt_gpu_li_device's. With n_dims = 0, or both cursors equal to n_dims, no
+ * value is stratified and every output is pbrt_gpu_li_device's, bit for bit
+ * (with n_dims = 0, s1d, table and k are not read and may be NULL).
+ *
+ * table[i] and k[i] index memory: the kernel clamps them into [0, n_tables) and
+ * [0, spp). A ray whose values were out of range gets an unspecified radiance;
+ * other rays are unaffected, and no address outside the caller's arrays is
+ * formed. One kernel launch (k_li_strat) in the steady state, as k_li.
+ *
+ * PBRT_E_INVALID: pbrt_gpu_li_device's cases; a NULL strat; strat->reserved !=
+ * 0; n_dims < 0; a cursor outside [0, n_dims]; and, while n_dims > 0, a NULL
+ * s1d, table or k, spp < 1 or n_tables < 1. */
+typedef struct pbrt_strat_soa {
+    const double* s1d;           /* [n_tables][n_dims * spp]                      */
+    const int32_t *table, *k;    /* per ray                                       */
+    int32_t n_tables, spp, n_dims;
+    int32_t first_1d, first_2d;  /* 0..n_dims                                     */
+    int32_t reserved;            /* 0                                             */
+} pbrt_strat_soa;
+int pbrt_gpu_li_stratified_device(pbrt_gpu_ctx* ctx, const pbrt_li_desc* desc, const pbrt_ray_soa* rays,
+                                  const pbrt_rng_soa* rng, size_t n, const pbrt_radiance_soa* out,
+                                  const pbrt_strat_soa* strat);
 
 /* Cancels the render in flight on ctx (from pbrt_gpu_render[_async[_into]]
  * entry until its pbrt_gpu_synchronize returns): the kernels poll a flag between

@@ -518,28 +518,81 @@ type DeviceRadiance struct{ R, G, B, State, Draws, Rays *DeviceBuffer }
 // rough glass are refused with the reason.
 func (r *Renderer) LiDevice(rays DeviceRays, rng DeviceRNG, n int, maxDepth int32, rrThreshold float64,
 	strategy int32, out DeviceRadiance) error {
-	soa, err := r.raySoA(rays, n)
+	soa, gs, rs, err := r.liSoAs(rays, rng, n, out)
 	if err != nil {
 		return err
 	}
+	ld := liDesc(maxDepth, rrThreshold, strategy)
+	if rc := C.pbrt_gpu_li_device(r.ctx, &ld, &soa, &gs, C.size_t(n), &rs); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_li_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// liSoAs are the ray, rng and radiance structs of a Li query over buffers checked to hold n elements.
+func (r *Renderer) liSoAs(rays DeviceRays, rng DeviceRNG, n int, out DeviceRadiance) (C.pbrt_ray_soa, C.pbrt_rng_soa,
+	C.pbrt_radiance_soa, error) {
 	var gs C.pbrt_rng_soa
 	var rs C.pbrt_radiance_soa
+	soa, err := r.raySoA(rays, n)
+	if err != nil {
+		return soa, gs, rs, err
+	}
 	p := [8]unsafe.Pointer{}
 	elem := [8]int{8, 8, 8, 8, 8, 8, 4, 4}
 	for k, d := range []*DeviceBuffer{rng.State, rng.Inc, out.R, out.G, out.B, out.State, out.Draws, out.Rays} {
 		if p[k], err = r.devPtr(d, n, elem[k], k > 4); err != nil {
-			return err
+			return soa, gs, rs, err
 		}
 	}
 	gs.state, gs.inc = (*C.uint64_t)(p[0]), (*C.uint64_t)(p[1])
 	rs.r, rs.g, rs.b = (*C.double)(p[2]), (*C.double)(p[3]), (*C.double)(p[4])
 	rs.state, rs.draws, rs.rays = (*C.uint64_t)(p[5]), (*C.uint32_t)(p[6]), (*C.uint32_t)(p[7])
+	return soa, gs, rs, nil
+}
+
+func liDesc(maxDepth int32, rrThreshold float64, strategy int32) C.pbrt_li_desc {
 	var ld C.pbrt_li_desc
 	ld.integrator, ld.max_depth = C.PBRT_INTEGRATOR_PATH, C.int32_t(maxDepth)
 	ld.light_strategy, ld.reserved = C.int32_t(strategy), 0
 	ld.rr_threshold = C.double(rrThreshold)
-	if rc := C.pbrt_gpu_li_device(r.ctx, &ld, &soa, &gs, C.size_t(n), &rs); rc != C.PBRT_OK {
-		return fmt.Errorf("pbrt_gpu_li_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	return ld
+}
+
+// LiStratifiedDevice is LiDevice under the stratified sampler
+// (pbrt_gpu_li_stratified_device): ray i samples with a PixelSampler whose tables
+// are strat.S1D[strat.Table[i]] (nTables tables of nDims * spp values), at sample
+// strat.K[i], with its cursors at (first1D, first2D), on the stream (State[i],
+// Inc[i]). Draws counts PCG32 draws only. Table and K are clamped on the device:
+// an out-of-range value gives that ray an unspecified radiance and touches no
+// other. With nDims 0 strat may be empty, and the call is LiDevice.
+func (r *Renderer) LiStratifiedDevice(rays DeviceRays, rng DeviceRNG, n int, maxDepth int32, rrThreshold float64,
+	strategy int32, out DeviceRadiance, strat DeviceStrat, nTables, spp, nDims, first1D, first2D int32) error {
+	soa, gs, rs, err := r.liSoAs(rays, rng, n, out)
+	if err != nil {
+		return err
+	}
+	var st C.pbrt_strat_soa
+	if nDims > 0 {
+		if nTables < 1 || spp < 1 {
+			return fmt.Errorf("pbrtgpu: LiStratifiedDevice: nTables and spp must be >= 1")
+		}
+		p := [3]unsafe.Pointer{}
+		if p[0], err = r.devPtr(strat.S1D, int(nTables)*int(nDims)*int(spp), 8, false); err != nil {
+			return err
+		}
+		for k, d := range []*DeviceBuffer{strat.Table, strat.K} {
+			if p[1+k], err = r.devPtr(d, n, 4, false); err != nil {
+				return err
+			}
+		}
+		st.s1d, st.table, st.k = (*C.double)(p[0]), (*C.int32_t)(p[1]), (*C.int32_t)(p[2])
+	}
+	st.n_tables, st.spp, st.n_dims = C.int32_t(nTables), C.int32_t(spp), C.int32_t(nDims)
+	st.first_1d, st.first_2d, st.reserved = C.int32_t(first1D), C.int32_t(first2D), 0
+	ld := liDesc(maxDepth, rrThreshold, strategy)
+	if rc := C.pbrt_gpu_li_stratified_device(r.ctx, &ld, &soa, &gs, C.size_t(n), &rs, &st); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_li_stratified_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
 	}
 	return nil
 }
@@ -807,25 +860,100 @@ func (r *Renderer) FrameSamplesDevice(f FrameRange, out DeviceSamples) error {
 	if err != nil {
 		return err
 	}
-	soa, err := r.raySoA(out.Rays, n)
+	s, err := r.samplesSoA(out, n)
 	if err != nil {
 		return err
+	}
+	d := f.desc(0)
+	if rc := C.pbrt_gpu_frame_samples_device(r.ctx, &d, &s); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_frame_samples_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	}
+	return nil
+}
+
+// samplesSoA is pbrt_frame_samples_soa over the buffers of out, each checked to hold n elements.
+func (r *Renderer) samplesSoA(out DeviceSamples, n int) (C.pbrt_frame_samples_soa, error) {
+	var s C.pbrt_frame_samples_soa
+	soa, err := r.raySoA(out.Rays, n)
+	if err != nil {
+		return s, err
 	}
 	p := [6]unsafe.Pointer{}
 	elem := [6]int{8, 8, 8, 8, 4, 4}
 	for k, d := range []*DeviceBuffer{out.PFilmX, out.PFilmY, out.RNG.State, out.RNG.Inc, out.Px, out.Py} {
 		if p[k], err = r.devPtr(d, n, elem[k], k > 3); err != nil {
-			return err
+			return s, err
 		}
 	}
-	var s C.pbrt_frame_samples_soa
 	s.ox, s.oy, s.oz, s.dx, s.dy, s.dz, s.tmax = soa.ox, soa.oy, soa.oz, soa.dx, soa.dy, soa.dz, soa.tmax
 	s.pfilm_x, s.pfilm_y = (*C.double)(p[0]), (*C.double)(p[1])
 	s.state, s.inc = (*C.uint64_t)(p[2]), (*C.uint64_t)(p[3])
 	s.px, s.py = (*C.int32_t)(p[4]), (*C.int32_t)(p[5])
+	return s, nil
+}
+
+// StratSampler is pbrt_strat_sampler_desc: sampler.NewStratified(X, Y, Jitter, NDims).
+type StratSampler struct {
+	X, Y, NDims int32
+	Jitter      bool
+}
+
+// CameraCursors are the dimensions a path's first Get1D / Get2D read after
+// GetCameraSample (pFilm, pLens, time): what LiStratifiedDevice takes as
+// first1D, first2D for the samples of FrameSamplesStratified.
+func (s StratSampler) CameraCursors() (first1D, first2D int32) {
+	first1D, first2D = 1, 2
+	if s.NDims < 1 {
+		first1D = s.NDims
+	}
+	if s.NDims < 2 {
+		first2D = s.NDims
+	}
+	return
+}
+
+// DeviceStrat are the stratified sampler's arrays: S1D (float64) holds the
+// tables, NDims * spp values each; Table and K (int32) are the table and the
+// sample index of each sample or ray.
+type DeviceStrat struct{ S1D, Table, K *DeviceBuffer }
+
+// FrameSamplesStratified enqueues the traced samples (k = 1 .. spp - 1) of a
+// THROUGHPUT render under the stratified sampler s, NDims >= 1, over a tile range
+// (pbrt_gpu_frame_samples_stratified_device): f.Ns must be spp - 1. It writes
+// FrameSamplesDevice's outputs, K and Table per sample, and the table of every
+// pixel of the range to strat.S1D. One kernel; nothing is copied or waited for.
+func (r *Renderer) FrameSamplesStratified(f FrameRange, s StratSampler, out DeviceSamples, strat DeviceStrat) error {
+	n, err := r.FrameCount(f)
+	if err != nil {
+		return err
+	}
+	soa, err := r.samplesSoA(out, n)
+	if err != nil {
+		return err
+	}
+	if f.Ns < 1 || s.X < 1 || s.Y < 1 || s.NDims < 0 {
+		return fmt.Errorf("pbrtgpu: FrameSamplesStratified: bad sampler or ns")
+	}
+	var ss C.pbrt_strat_samples_soa
+	pixels := n / int(f.Ns)
+	p := [3]unsafe.Pointer{}
+	for k, d := range []*DeviceBuffer{strat.K, strat.Table} {
+		if p[k], err = r.devPtr(d, n, 4, false); err != nil {
+			return err
+		}
+	}
+	if p[2], err = r.devPtr(strat.S1D, pixels*int(s.NDims)*int(s.X)*int(s.Y), 8, false); err != nil {
+		return err
+	}
+	ss.k, ss.table, ss.s1d = (*C.int32_t)(p[0]), (*C.int32_t)(p[1]), (*C.double)(p[2])
+	var sd C.pbrt_strat_sampler_desc
+	sd.sampler_x, sd.sampler_y, sd.n_dims, sd.reserved = C.int32_t(s.X), C.int32_t(s.Y), C.int32_t(s.NDims), 0
+	if s.Jitter {
+		sd.jitter = 1
+	}
 	d := f.desc(0)
-	if rc := C.pbrt_gpu_frame_samples_device(r.ctx, &d, &s); rc != C.PBRT_OK {
-		return fmt.Errorf("pbrt_gpu_frame_samples_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
+	if rc := C.pbrt_gpu_frame_samples_stratified_device(r.ctx, &d, &sd, &soa, &ss); rc != C.PBRT_OK {
+		return fmt.Errorf("pbrt_gpu_frame_samples_stratified_device: %s", C.GoString(C.pbrt_gpu_last_error(r.ctx)))
 	}
 	return nil
 }
